@@ -22,11 +22,19 @@ merge when N>1) + hash join + filter.  The first step additionally pays
 SQL parse + DAG build + spec-uuid hashing; subsequent identical calls
 replay the built plan through the framework's plan cache
 (``fugue_amd/sql/api.py`` — a prepared-statement cache; execution always
-reruns) exactly as a production driver loop would.  The raw engine-op
-step time (no FugueSQL/workflow layer) is also measured and reported as
-``config.engine_ops_ms_per_step``.
+reruns) exactly as a production driver loop would.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time ``--steps`` steps, print the result line.  ``--full`` additionally
+measures the raw engine-op step time (no FugueSQL/workflow layer) and
+reports it as ``config.engine_ops_ms_per_step``.  ``--dump-outputs DIR``
+writes the columns of the last timed step's result frame (what the
+``fa.fugue_sql`` caller received) as ``DIR/<column>.npy`` in float64,
+rows sorted by key because the engine's row order is not defined; inputs
+are seeded, so two builds can be compared output for output.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R]
+                        [--dump-outputs DIR] [--full]
 The driver launches N>1 via torch.distributed.run (one rank per GPU).
 """
 import argparse
@@ -41,6 +49,8 @@ import torch
 ROWS_PER_GPU_DEFAULT = 125_000_000  # 1e9 / 8 GPUs
 N_GROUPS = 1_000_000
 DIM_ROWS = 1_000_000
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+DUMP_SAMPLE_SEED = 1234
 
 FLAGSHIP_SQL = """
 t = TRANSFORM fact USING scale SCHEMA k:long,v:double
@@ -51,6 +61,61 @@ YIELD DATAFRAME AS result
 """
 
 
+def dump_outputs(out, directory: str, rank: int, world: int) -> None:
+    """Write each column of result frame ``out`` as float64 ``.npy``.
+
+    The engine returns the result rows in no defined order (the group-by
+    and join emit through atomics), so the rows are written sorted by the
+    columns in schema order (``k`` first, which is unique) to make two
+    runs comparable row for row.  Rank r>0 of a multi-GPU run writes
+    ``<column>.rank<r>.npy`` (its own shard).  A frame above
+    ``DUMP_MAX_BYTES`` is cut to a fixed seeded sample of the sorted rows
+    (same rows for every column)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for name, c in out.columns_map.items():
+        arr = c.data.detach().cpu().numpy().astype(np.float64)
+        if c.valid is not None:
+            arr[~c.valid.detach().cpu().numpy().astype(bool)] = np.nan
+        arrays[name] = arr
+    names = list(arrays)
+    idx = np.lexsort([arrays[x] for x in reversed(names)])
+    max_rows = DUMP_MAX_BYTES // (8 * max(1, len(names)))
+    if len(idx) > max_rows:
+        keep = np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+            len(idx), size=max_rows, replace=False
+        )
+        idx = idx[np.sort(keep)]
+    suffix = ".npy" if world == 1 or rank == 0 else f".rank{rank}.npy"
+    for name in names:
+        np.save(os.path.join(directory, name + suffix), arrays[name][idx])
+
+
+def use_prebuilt_extension() -> None:
+    """Load the extension ``build()`` left in the tree when the benchmark's
+    user cannot write there (a checkout built by someone else).
+
+    The JIT loader takes a lock file in the build directory even when the
+    library is up to date, so it fails on a read-only tree.  Nothing could
+    be rebuilt there anyway: import the built library as it is.  A missing
+    library stays an error (the normal loader raises at the first step)."""
+    import importlib.util
+
+    import fugue_amd.hip.ext as ext
+
+    lib = os.path.join(ext._BUILD_DIR, "fugue_amd_hip.so")
+    if (
+        ext._EXT is not None
+        or not os.path.isfile(lib)
+        or os.access(ext._BUILD_DIR, os.W_OK)
+    ):
+        return
+    spec = importlib.util.spec_from_file_location("fugue_amd_hip", lib)
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    ext._EXT = module
+
+
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--gpus", type=int, default=1)
@@ -58,7 +123,15 @@ def main() -> None:
     parser.add_argument("--warmup", type=int, default=10)
     parser.add_argument("--rows", type=int, default=ROWS_PER_GPU_DEFAULT,
                         help="rows per GPU (weak scaling)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="write the last timed step's result columns "
+                             "as DIR/<column>.npy")
+    parser.add_argument("--full", action="store_true",
+                        help="also measure the secondary figures "
+                             "(raw engine-op step time)")
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -72,6 +145,7 @@ def main() -> None:
     import pyarrow as pa
     from fugue_amd.schema import Schema
 
+    use_prebuilt_extension()
     engine = HipExecutionEngine()
     device = torch.device(engine.device)
 
@@ -140,12 +214,13 @@ def main() -> None:
             torch.cuda.synchronize()
         engine.comm.barrier()
 
-    def timed(fn, steps: int) -> float:
+    def timed(fn, steps: int):
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             fn()
+        last = fn()  # the last timed step's result is what gets dumped
         sync()
-        return time.perf_counter() - t0
+        return time.perf_counter() - t0, last
 
     def max_over_ranks(elapsed: float) -> float:
         if engine.comm.is_distributed:
@@ -162,16 +237,24 @@ def main() -> None:
     for _ in range(args.warmup):
         step()
     sync()
-    elapsed = max_over_ranks(timed(step, args.steps))
-    out = step()
-
-    # secondary: raw engine ops (fixed small step count)
-    eo_steps = max(5, args.steps // 10)
-    for _ in range(2):
-        engine_ops_step()
-    sync()
-    eo_elapsed = max_over_ranks(timed(engine_ops_step, eo_steps))
+    elapsed, out = timed(step, args.steps)
+    elapsed = max_over_ranks(elapsed)
     out_count = out.count()
+    if args.dump_outputs is not None:
+        dump_outputs(out, args.dump_outputs, rank, world)
+
+    config_extra = {}
+    if args.full:
+        # secondary: raw engine ops (fixed small step count)
+        eo_steps = max(5, args.steps // 10)
+        for _ in range(2):
+            engine_ops_step()
+        sync()
+        eo_elapsed, _ = timed(engine_ops_step, eo_steps)
+        eo_elapsed = max_over_ranks(eo_elapsed)
+        config_extra["engine_ops_ms_per_step"] = round(
+            eo_elapsed / eo_steps * 1000.0, 3
+        )
 
     total_rows = n * world
     rows_per_sec = total_rows * args.steps / elapsed
@@ -202,9 +285,7 @@ def main() -> None:
                         dim_rows=DIM_ROWS,
                         parallelism=f"dp{world}",
                         out_rows=out_count,
-                        engine_ops_ms_per_step=round(
-                            eo_elapsed / eo_steps * 1000.0, 3
-                        ),
+                        **config_extra,
                     ),
                 )
             ),

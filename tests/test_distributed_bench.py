@@ -28,6 +28,10 @@ def _torchrun(nproc: int, script: str, *args: str, timeout: int = 420) -> str:
     env.pop("LOCAL_RANK", None)
     env.pop("MASTER_ADDR", None)
     env.pop("MASTER_PORT", None)
+    # gloo/CPU ranks: the workers must not see a GPU the host may have
+    # (N ranks cannot share one device)
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
     cmd = [
         sys.executable, "-m", "torch.distributed.run",
         "--nnodes=1", f"--nproc-per-node={nproc}",

@@ -16,6 +16,7 @@ import torch
 import torch.multiprocessing as mp
 
 WORLD = 2
+_NO_GPU_ENV = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
 
 
 def _run_worker(rank: int, world: int, port: int, fn_bytes: bytes, out_q) -> None:
@@ -55,8 +56,19 @@ def run_distributed(fn: Callable[[int], Any], port: int) -> Dict[int, Any]:
         ctx.Process(target=_run_worker, args=(r, WORLD, port, pickle.dumps(fn), q))
         for r in range(WORLD)
     ]
-    for p in procs:
-        p.start()
+    # gloo/CPU ranks: the spawned workers must not see a GPU the host may
+    # have (the ranks cannot share one device)
+    saved = {k: os.environ.get(k) for k in _NO_GPU_ENV}
+    os.environ.update(_NO_GPU_ENV)
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     results: Dict[int, Any] = {}
     try:
         for _ in range(WORLD):
@@ -231,10 +243,15 @@ def test_distributed_q3():
     from fugue_amd.hip.execution_engine import HipExecutionEngine
 
     e = HipExecutionEngine()
-    customer, orders, lineitem, _ = gen_tables(0.005, e.device, 0)
+    # same generator device as the ranks: the tables are a function of it
+    customer, orders, lineitem, _ = gen_tables(0.005, "cpu", 0)
     expected = fa.fugue_sql(
-        Q3, customer=customer, orders=orders, lineitem=lineitem,
-        engine=e, as_fugue=True,
+        Q3,
+        customer=customer.as_pandas(),
+        orders=orders.as_pandas(),
+        lineitem=lineitem.as_pandas(),
+        engine=e,
+        as_fugue=True,
     )
     exp = sorted(map(tuple, expected.as_array()))
     for rank, got in results.items():

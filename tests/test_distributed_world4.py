@@ -10,6 +10,7 @@ import pandas as pd
 import torch.multiprocessing as mp
 
 WORLD = 4
+_NO_GPU_ENV = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
 
 
 def _run_worker(rank: int, world: int, port: int, fn_bytes: bytes, out_q) -> None:
@@ -51,8 +52,19 @@ def run_world4(fn: Callable[[int], Any], port: int) -> Dict[int, Any]:
         )
         for r in range(WORLD)
     ]
-    for p in procs:
-        p.start()
+    # gloo/CPU ranks: the spawned workers must not see a GPU the host may
+    # have (4 ranks cannot share one device)
+    saved = {k: os.environ.get(k) for k in _NO_GPU_ENV}
+    os.environ.update(_NO_GPU_ENV)
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     results: Dict[int, Any] = {}
     try:
         for _ in range(WORLD):
