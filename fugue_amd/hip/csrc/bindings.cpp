@@ -105,6 +105,12 @@ void launch_cmp_imm(const void*, const bool*, int, int64_t, double, int,
                     int, int64_t, bool*, hipStream_t);
 void launch_cmp_col(const void*, const bool*, const void*, const bool*, int,
                     int, int64_t, bool*, hipStream_t);
+void launch_seg_rank(const int64_t*, const int64_t*, const int64_t* const*,
+                     const uint8_t* const*, const int*, int, int64_t, int,
+                     int64_t*, int64_t*, hipStream_t);
+void launch_seg_take(const int64_t*, const int64_t*, int64_t, int64_t,
+                     int64_t*, int64_t*, int64_t*, int64_t*, hipStream_t);
+int64_t seg_rank_chunk_size();
 void launch_gb_compact(const int64_t*, const int64_t*, const double**,
                        double**, int, int64_t, int64_t*, int64_t*, int64_t*,
                        int64_t*, const int64_t*, int64_t*, hipStream_t);
@@ -964,6 +970,83 @@ std::vector<at::Tensor> gb_compact(at::Tensor tkeys, at::Tensor gcount,
   return {out_keys, out_count, out_aggs, out_extra, bases};
 }
 
+// Segmented rank over a sorted permutation, window mode: the rank of each
+// row lands at its ORIGINAL row position.  kind 0 row_number, 1 rank,
+// 2 dense_rank.  Order columns are 8-byte (int64 bits or float64) in
+// original row order, each with an optional bool validity tensor.
+int64_t seg_rank_chunk() { return seg_rank_chunk_size(); }
+
+static void seg_check_inputs(const at::Tensor& perm, const at::Tensor& pkeys) {
+  check_gpu(perm, "perm");
+  check_gpu(pkeys, "pkeys");
+  TORCH_CHECK(perm.scalar_type() == at::kLong && perm.is_contiguous(),
+              "perm must be contiguous int64");
+  TORCH_CHECK(pkeys.scalar_type() == at::kLong && pkeys.is_contiguous(),
+              "pkeys must be contiguous int64");
+  TORCH_CHECK(perm.numel() == pkeys.numel(), "perm/pkeys length mismatch");
+}
+
+at::Tensor seg_rank(at::Tensor perm, at::Tensor pkeys,
+                    std::vector<at::Tensor> col_data,
+                    std::vector<c10::optional<at::Tensor>> col_valid,
+                    int64_t kind) {
+  seg_check_inputs(perm, pkeys);
+  int64_t n = perm.numel();
+  int ncols = (int)col_data.size();
+  TORCH_CHECK(ncols <= 4, "at most 4 order columns");
+  TORCH_CHECK(col_valid.size() == col_data.size(), "col_valid size mismatch");
+  TORCH_CHECK(kind >= 0 && kind <= 2, "kind must be 0, 1 or 2");
+  const int64_t* cd[4] = {nullptr, nullptr, nullptr, nullptr};
+  const uint8_t* cv[4] = {nullptr, nullptr, nullptr, nullptr};
+  int cf[4] = {0, 0, 0, 0};
+  for (int c = 0; c < ncols; ++c) {
+    check_gpu(col_data[c], "order column");
+    TORCH_CHECK(col_data[c].is_contiguous() && col_data[c].numel() == n &&
+                    col_data[c].element_size() == 8,
+                "order columns must be contiguous 8-byte tensors of length n");
+    cf[c] = col_data[c].is_floating_point() ? 1 : 0;
+    cd[c] = reinterpret_cast<const int64_t*>(col_data[c].data_ptr());
+    if (col_valid[c].has_value()) {
+      const at::Tensor& v = *col_valid[c];
+      check_gpu(v, "order validity");
+      TORCH_CHECK(v.scalar_type() == at::kBool && v.is_contiguous() &&
+                      v.numel() == n,
+                  "validity must be contiguous bool of length n");
+      cv[c] = reinterpret_cast<const uint8_t*>(v.data_ptr());
+    }
+  }
+  auto out = at::empty({n}, perm.options());
+  if (n == 0) return out;
+  int64_t chunk = seg_rank_chunk_size();
+  int64_t nblocks = (n + chunk - 1) / chunk;
+  auto work = at::empty({6 * nblocks}, perm.options());
+  launch_seg_rank(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(), cd, cv,
+                  cf, ncols, n, (int)kind, work.data_ptr<int64_t>(),
+                  out.data_ptr<int64_t>(), current_stream());
+  return out;
+}
+
+// Take mode: the first n_take sorted positions of every segment, emitted
+// as a capacity-n index vector in sorted order plus the block-base scan
+// whose last element is the total (single host read; caller narrows).
+std::vector<at::Tensor> seg_take(at::Tensor perm, at::Tensor pkeys,
+                                 int64_t n_take) {
+  seg_check_inputs(perm, pkeys);
+  int64_t n = perm.numel();
+  int64_t chunk = seg_rank_chunk_size();
+  int64_t nblocks = (n + chunk - 1) / chunk;
+  auto out = at::empty({n}, perm.options());
+  if (n == 0) return {out, at::zeros({1}, perm.options())};
+  auto work = at::empty({6 * nblocks}, perm.options());
+  auto bcounts = at::empty({nblocks}, perm.options());
+  auto bases = at::empty({nblocks + 1}, perm.options());
+  launch_seg_take(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(), n,
+                  n_take, work.data_ptr<int64_t>(),
+                  bcounts.data_ptr<int64_t>(), bases.data_ptr<int64_t>(),
+                  out.data_ptr<int64_t>(), current_stream());
+  return {out, bases};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hash_column", &hash_column,
         "combine a column into the running row hash");
@@ -994,6 +1077,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused key min/max + sampled distinct estimate");
   m.def("pack_columns", &pack_columns, "pack key columns into int64");
   m.def("unpack_column", &unpack_column, "unpack one key column");
+  m.def("seg_rank_chunk", &seg_rank_chunk,
+        "sorted positions per block of the segmented rank kernels");
+  m.def("seg_rank", &seg_rank,
+        "segmented row_number/rank/dense_rank in original row order");
+  m.def("seg_take", &seg_take,
+        "deterministic first-n-per-segment index vector");
   m.def("gb_compact", &gb_compact,
         "deterministic group-table compaction");
   m.def("compact_columns_cap", &compact_columns_cap,

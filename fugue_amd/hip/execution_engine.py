@@ -1422,6 +1422,16 @@ class HipExecutionEngine(ExecutionEngine):
         na_position: str = "last",
         partition_spec: Optional[PartitionSpec] = None,
     ) -> DataFrame:
+        """First ``n`` rows by ``presort``, globally or per partition.
+
+        A partitioned take on a device frame stays in HBM: the shard is
+        hash-repartitioned by the partition columns (distributed), sorted
+        stably by (partition identity, presort), and the first ``n``
+        sorted positions of every partition are kept by the segmented
+        rank kernels; the result stays sharded.  Ties at the cut are
+        broken by original row order, because the sort is stable.  String
+        presort columns, float partition keys and a string-key hash
+        collision take the host path."""
         if not isinstance(n, int):
             raise ValueError("n needs to be an integer")
         partition_spec = partition_spec or PartitionSpec()
@@ -1447,6 +1457,26 @@ class HipExecutionEngine(ExecutionEngine):
                 ).head(n)
             return pdf.reset_index(drop=True)
 
+        if (
+            isinstance(d, HipDataFrame)
+            and len(partition_spec.partition_by) > 0
+            and n >= 0
+            and na_position in ("first", "last")
+        ):
+            try:
+                with op_range("fugue.take.partitioned"):
+                    res = self._take_partitioned_device(
+                        d,
+                        n,
+                        list(partition_spec.partition_by),
+                        list(_presort.keys()),
+                        list(_presort.values()),
+                        na_position,
+                    )
+                self._stats.add("take.device_partitioned")
+                return res
+            except NotImplementedError:
+                pass
         if (
             isinstance(d, HipDataFrame)
             and len(partition_spec.partition_by) == 0
@@ -1524,6 +1554,153 @@ class HipExecutionEngine(ExecutionEngine):
             PandasDataFrame(local, d.schema),
             shard_replicated=self.is_distributed,
         )
+
+    # ------------------------------------------------------------------ #
+    # per-partition take / ranking windows: segmented rank kernels         #
+    # ------------------------------------------------------------------ #
+    def _check_rank_shape(
+        self, d: HipDataFrame, keys: List[str], order_names: List[str]
+    ) -> None:
+        """Schema-only checks (identical on every rank, so a fallback
+        decision never splits the ranks of a distributed run)."""
+        for k in keys:
+            c = d.col(k)
+            if (
+                not isinstance(c, StringDeviceColumn)
+                and c.data.is_floating_point()
+            ):
+                # value-equality of floats (-0.0 == 0.0, NaN as null) has
+                # no exact packed or hashed identity
+                raise NotImplementedError("float partition keys")
+        for name in order_names:
+            if isinstance(d.col(name), StringDeviceColumn):
+                raise NotImplementedError("string presort")
+
+    def _partition_sort(
+        self,
+        d: HipDataFrame,
+        keys: List[str],
+        order_names: List[str],
+        order_asc: List[bool],
+        na_position: str,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(partition identity in row order, stable sort permutation by
+        (identity, order columns)).  Identity resolution is the keyed
+        ``map_dataframe`` one: exact ``pack_keys`` when possible, else the
+        64-bit row hash verified with the ``_H2_SEED`` second hash on
+        adjacent sorted rows; null keys form their own group."""
+        key_cols = [d.col(k) for k in keys]
+        h2v: Optional[torch.Tensor] = None
+        try:
+            pkeys, _ = dops.pack_keys(key_cols)
+        except NotImplementedError:
+            pkeys = dops.hash_rows(key_cols)
+            h2v = dops.hash_rows(key_cols, seed=dops._H2_SEED)
+        pkeys = pkeys.contiguous()
+        perm = dops.sort_indices_exact(
+            d, order_names, order_asc, na_position, key_tensor=pkeys
+        )
+        if h2v is not None:
+            collided = 0
+            if perm.numel() > 1:
+                s1 = pkeys.index_select(0, perm)
+                s2 = h2v.index_select(0, perm)
+                same1 = s1[1:] == s1[:-1]
+                collided = int(
+                    bool((same1 & (s2[1:] != s2[:-1])).any().item())
+                )
+            if self.is_distributed:
+                # every rank must take the same path
+                collided = int(self._comm.allreduce_sum(collided))
+            if collided > 0:
+                raise NotImplementedError("string key hash collision")
+        return pkeys, perm
+
+    def _take_partitioned_device(
+        self,
+        d: HipDataFrame,
+        n: int,
+        keys: List[str],
+        order_names: List[str],
+        order_asc: List[bool],
+        na_position: str,
+    ) -> HipDataFrame:
+        if os.environ.get("FUGUE_HIP_FORCE_HOST_TAKE", "") == "1":
+            # A/B probe (benchmarks/take_group_bench.py): the host path
+            raise NotImplementedError("host take forced")
+        self._check_rank_shape(d, keys, order_names)
+        if self.is_distributed:
+            d = self._shuffle_by_columns(d, keys)
+        pkeys, perm = self._partition_sort(
+            d, keys, order_names, order_asc, na_position
+        )
+        idx = dops.take_per_group_indices(perm, pkeys, n)
+        return d.gather_rows(idx)
+
+    def rank_over(
+        self,
+        df: DataFrame,
+        partition_by: List[str],
+        order_by: List[Tuple[str, bool]],
+        kind: str,
+        name: str,
+    ) -> DataFrame:
+        """``df`` plus one ranking-window column ``name``:
+        ``kind`` in ``row_number`` / ``rank`` / ``dense_rank`` over
+        (PARTITION BY ``partition_by`` ORDER BY ``order_by``), where
+        ``order_by`` is a list of ``(column, ascending)`` pairs and nulls
+        sort last.  ``row_number`` breaks ties by original row order.
+        ``row_number`` and ``dense_rank`` are ``long``; ``rank`` is
+        ``double``, which is what the host SQL executor yields.  Raises
+        ``NotImplementedError`` for shapes that stay on the host."""
+        d = self.to_df(df)
+        if not isinstance(d, HipDataFrame):
+            raise NotImplementedError("rank_over needs a device frame")
+        if kind not in dops.RANK_KINDS:
+            raise NotImplementedError(f"window function {kind}")
+        if len(partition_by) == 0:
+            raise NotImplementedError("window without PARTITION BY")
+        if name in d.schema:
+            raise NotImplementedError(f"column {name} already exists")
+        order_names = [c for c, _ in order_by]
+        order_asc = [bool(a) for _, a in order_by]
+        if kind != "row_number" and not 1 <= len(order_names) <= 4:
+            raise NotImplementedError("rank needs 1..4 ORDER BY columns")
+        keys = list(partition_by)
+        self._check_rank_shape(d, keys, order_names)
+        total = d.count()
+        if self.is_distributed:
+            total = int(self._comm.allreduce_sum(total))
+        if total == 0:
+            # the host executor types an empty window column as double
+            raise NotImplementedError("window over an empty frame")
+        with op_range("fugue.window.rank"):
+            if self.is_distributed:
+                d = self._shuffle_by_columns(d, keys)
+            pkeys, perm = self._partition_sort(
+                d, keys, order_names, order_asc, "last"
+            )
+            order_cols: List[Any] = []
+            if kind != "row_number":
+                for oname in order_names:
+                    c = d.col(oname)
+                    data, valid = c.data, c.valid
+                    if data.is_floating_point():
+                        # the sort placed NaN with the nulls; rank them
+                        # as nulls too (host executor: isna)
+                        nan = torch.isnan(data)
+                        valid = ~nan if valid is None else (valid & ~nan)
+                    order_cols.append((data, valid))
+            ranks = dops.segmented_rank(perm, pkeys, order_cols, kind)
+        if kind == "rank":
+            out_col = DeviceColumn(ranks.to(torch.float64), None, pa.float64())
+        else:
+            out_col = DeviceColumn(ranks, None, pa.int64())
+        cols = dict(d.columns_map)
+        cols[name] = out_col
+        schema = d.schema + Schema([(name, out_col.pa_type)])
+        self._stats.add("window.device")
+        return HipDataFrame.from_columns(cols, schema, self._device)
 
     # ------------------------------------------------------------------ #
     # select / aggregate: device fast path                                 #

@@ -1181,3 +1181,171 @@ def group_boundaries(sorted_keys: torch.Tensor) -> torch.Tensor:
     change = torch.ones(n, dtype=torch.bool, device=sorted_keys.device)
     change[1:] = sorted_keys[1:] != sorted_keys[:-1]
     return change.nonzero(as_tuple=True)[0]
+
+
+# ------------------------------------------------------------------ #
+# segmented rank over a sorted permutation                             #
+# ------------------------------------------------------------------ #
+RANK_KINDS = {"row_number": 0, "rank": 1, "dense_rank": 2}
+
+
+def sort_indices_exact(
+    df: HipDataFrame,
+    by: List[str],
+    ascending: List[bool],
+    na_position: str = "last",
+    key_tensor: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Stable multi-key sort permutation like :func:`sort_indices`, but
+    nulls are placed by a separate stable pass over the validity flag
+    instead of a sentinel value: ``INT64_MAX``/``±inf`` stay distinct
+    from null and both ``na_position`` values work.  NaN counts as null
+    (pandas semantics).  ``key_tensor``, when given, is an int64 tensor
+    in row order that becomes the most significant (ascending) key."""
+    if na_position not in ("first", "last"):
+        raise ValueError(f"invalid na_position {na_position!r}")
+    n = df.count()
+    device = (
+        key_tensor.device if key_tensor is not None else torch.device(df.device)
+    )
+    perm = torch.arange(n, dtype=torch.int64, device=device)
+    for name, asc in reversed(list(zip(by, ascending))):
+        c = df.col(name)
+        if isinstance(c, StringDeviceColumn):
+            raise NotImplementedError("string sort keys not yet on device")
+        vals = c.data.index_select(0, perm)
+        if vals.dtype == torch.bool:
+            vals = vals.to(torch.uint8)
+        isnull: Optional[torch.Tensor] = None
+        if c.valid is not None:
+            isnull = ~c.valid.index_select(0, perm)
+        if vals.is_floating_point():
+            nan = torch.isnan(vals)
+            if bool(nan.any().item()):
+                isnull = nan if isnull is None else (isnull | nan)
+        if isnull is not None:
+            # values under a null must not influence the order
+            vals = torch.where(isnull, torch.zeros_like(vals), vals)
+        idx = torch.argsort(vals, stable=True, descending=not asc)
+        perm = perm.index_select(0, idx)
+        if isnull is not None:
+            flag = isnull.index_select(0, idx).to(torch.uint8)
+            if na_position == "first":
+                flag = 1 - flag
+            idx = torch.argsort(flag, stable=True)
+            perm = perm.index_select(0, idx)
+    if key_tensor is not None:
+        kv = key_tensor.index_select(0, perm)
+        idx = torch.argsort(kv, stable=True)
+        perm = perm.index_select(0, idx)
+    return perm
+
+
+def _order_col_parts(c: Any) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(8-byte data, validity) of an order column given as a
+    ``DeviceColumn`` or a ``(data, valid)`` pair; narrower dtypes widen."""
+    if isinstance(c, StringDeviceColumn):
+        raise NotImplementedError("string order columns not on device")
+    if isinstance(c, DeviceColumn):
+        data, valid = c.data, c.valid
+    else:
+        data, valid = c
+    if data.is_floating_point():
+        data = data.to(torch.float64)
+    else:
+        data = data.to(torch.int64)
+    return data.contiguous(), (None if valid is None else valid.contiguous())
+
+
+def _segment_flags_cpu(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    order_cols: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]],
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    n = perm.numel()
+    ks = pkeys.index_select(0, perm)
+    head = torch.ones(n, dtype=torch.bool)
+    head[1:] = ks[1:] != ks[:-1]
+    peer = head.clone()
+    for data, valid in order_cols:
+        v = data.index_select(0, perm)
+        eqv = v[1:] == v[:-1]
+        if v.is_floating_point():
+            eqv = eqv | (torch.isnan(v[1:]) & torch.isnan(v[:-1]))
+        if valid is not None:
+            ok = valid.index_select(0, perm)
+            eqv = torch.where(ok[1:] & ok[:-1], eqv, ok[1:] == ok[:-1])
+        peer[1:] |= ~eqv
+    return head, peer
+
+
+def _segmented_rank_cpu(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    order_cols: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]],
+    kind: int,
+) -> torch.Tensor:
+    """Ranks per SORTED position (not yet scattered to row order)."""
+    n = perm.numel()
+    head, peer = _segment_flags_cpu(perm, pkeys, order_cols)
+    pos = torch.arange(n, dtype=torch.int64)
+    zero = torch.zeros_like(pos)
+    seg_start = torch.cummax(torch.where(head, pos, zero), 0).values
+    if kind == 0:
+        return pos - seg_start + 1
+    if kind == 1:
+        peer_start = torch.cummax(torch.where(peer, pos, zero), 0).values
+        return peer_start - seg_start + 1
+    c = torch.cumsum(peer.to(torch.int64), 0)
+    return c - c.index_select(0, seg_start) + 1
+
+
+def segmented_rank(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    order_cols: Sequence[Any],
+    kind: str,
+) -> torch.Tensor:
+    """``row_number`` / ``rank`` / ``dense_rank`` of every row within its
+    partition, as int64 in ORIGINAL row order.
+
+    ``perm`` is a stable sort permutation by (partition key, order keys);
+    ``pkeys`` (int64) and ``order_cols`` are in original row order.  Each
+    order column is a ``DeviceColumn`` or a ``(data, valid)`` pair; rows
+    are peers when they share the partition and every order column is
+    equal (null equals null, NaN equals NaN).  ``row_number`` ignores the
+    order columns: ties keep the permutation's order."""
+    if kind not in RANK_KINDS:
+        raise ValueError(f"unknown rank kind {kind!r}")
+    k = RANK_KINDS[kind]
+    cols = [] if k == 0 else [_order_col_parts(c) for c in order_cols]
+    if len(cols) > 4:
+        raise NotImplementedError("at most 4 order columns on device")
+    perm = perm.contiguous()
+    pkeys = pkeys.contiguous()
+    n = perm.numel()
+    if _is_cpu(perm):
+        out = torch.empty(n, dtype=torch.int64)
+        if n > 0:
+            out[perm] = _segmented_rank_cpu(perm, pkeys, cols, k)
+        return out
+    return get_ext().seg_rank(
+        perm, pkeys, [c[0] for c in cols], [c[1] for c in cols], k
+    )
+
+
+def take_per_group_indices(
+    perm: torch.Tensor, pkeys: torch.Tensor, n: int
+) -> torch.Tensor:
+    """Row indices of the first ``n`` sorted positions of every partition,
+    in sorted order (deterministic).  Inputs as :func:`segmented_rank`."""
+    perm = perm.contiguous()
+    pkeys = pkeys.contiguous()
+    if perm.numel() == 0 or n <= 0:
+        return perm[:0]
+    if _is_cpu(perm):
+        rn = _segmented_rank_cpu(perm, pkeys, [], 0)
+        return perm[rn <= n]
+    out, bases = get_ext().seg_take(perm, pkeys, int(n))
+    total = int(bases[-1].item())  # the one host read of this op
+    return out.narrow(0, 0, total)

@@ -306,6 +306,65 @@ def _needed_columns(
     return needed
 
 
+_WINDOW_TMP = "_fugue_window_rank_"
+
+# Ranking windows the engine computes with its segmented rank kernels.
+# The lowered column keeps the type the pandas executor gives the same
+# text (measured on ``executor.WindowFunc.eval``): ROW_NUMBER is
+# ``cumcount() + 1`` and DENSE_RANK a ``cumsum`` of int64 flags, both
+# long; RANK goes through ``where``/``ffill`` and comes out double.
+# ``engine.rank_over`` yields exactly those types.  (Over an empty frame
+# the executor returns an empty float64 series for all three, so
+# ``rank_over`` declines empty input and the statement falls back.)
+_RANKING_WINDOWS = {
+    "ROW_NUMBER": "row_number",
+    "RANK": "rank",
+    "DENSE_RANK": "dense_rank",
+}
+
+
+def _find_ranking_window(
+    stmt: X.SelectStmt, schema: Schema
+) -> Optional[Tuple[int, str, List[str], List[Tuple[str, bool]]]]:
+    """(select index, kind, partition columns, order (column, asc) pairs)
+    of the statement's single lowerable ranking window; None when the
+    select list has no window item.  Raises UnsupportedPlan for every
+    other window shape."""
+    found = [
+        i for i, (e, _a) in enumerate(stmt.columns)
+        if isinstance(e, X.WindowFunc)
+    ]
+    if len(found) == 0:
+        return None
+    if len(found) > 1:
+        raise UnsupportedPlan("more than one window item")
+    if stmt.group_by or stmt.having is not None or stmt.distinct:
+        raise UnsupportedPlan("window with GROUP BY/HAVING/DISTINCT")
+    if stmt.joins:
+        raise UnsupportedPlan("window over a join")
+    w = stmt.columns[found[0]][0]
+    kind = _RANKING_WINDOWS.get(w.func.name)
+    if kind is None or len(w.func.args) > 0 or w.func.distinct:
+        raise UnsupportedPlan(f"window function {w.func.name}")
+    pcols: List[str] = []
+    for e in w.partition_by:
+        if not isinstance(e, X.ColRef) or e.name not in schema:
+            raise UnsupportedPlan("PARTITION BY expression")
+        pcols.append(e.name)
+    if len(pcols) == 0:
+        raise UnsupportedPlan("window without PARTITION BY")
+    ocols: List[Tuple[str, bool]] = []
+    for o in w.order_by:
+        if not isinstance(o.expr, X.ColRef) or o.expr.name not in schema:
+            raise UnsupportedPlan("window ORDER BY expression")
+        ocols.append((o.expr.name, bool(o.asc)))
+    if kind != "row_number" and len(ocols) == 0:
+        raise UnsupportedPlan(f"{w.func.name} requires ORDER BY")
+    if _WINDOW_TMP in schema:
+        raise UnsupportedPlan("reserved column name in input")
+    return found[0], kind, pcols, ocols
+
+
 def _execute_core(
     stmt: X.SelectStmt, tables: Dict[str, DataFrame], engine: Any
 ) -> DataFrame:
@@ -437,11 +496,29 @@ def _execute_core(
     cols: List[ColumnExpr] = []
     from fugue_amd.column.expressions import all_cols
 
+    window = _find_ranking_window(stmt, schema)
+    if window is not None:
+        # WHERE filters the rows the window sees, so it runs first
+        if where_expr is not None:
+            res = engine.select(
+                res, SelectColumns(all_cols()), where=where_expr
+            )
+            where_expr = None
+        win_idx, kind, pcols, ocols = window
+        res = engine.rank_over(res, pcols, ocols, kind, _WINDOW_TMP)
     for i, (e, alias) in enumerate(stmt.columns):
         if isinstance(e, X.Star):
             if e.qualifier is not None:
                 raise UnsupportedPlan("qualified * in select")
-            cols.append(all_cols())
+            if window is not None:
+                # the pre-window columns only: the rank column is
+                # projected under its own name below
+                cols.extend(col(n) for n in schema.names)
+            else:
+                cols.append(all_cols())
+            continue
+        if window is not None and i == window[0]:
+            cols.append(col(_WINDOW_TMP).alias(alias or e.default_name()))
             continue
         ce = _to_column_expr(e, schema, {})
         name = alias or e.default_name() or f"_col{i}"
