@@ -43,7 +43,19 @@ void launch_reduce_cols(const double*, const bool*, const int32_t*, int,
                         int64_t, double*, int64_t*, hipStream_t);
 void launch_gb_part_scatter(const int64_t*, const double*, int, int64_t, int,
                             int64_t*, int64_t*, double*, int, int32_t*,
-                            hipStream_t);
+                            int64_t, hipStream_t);
+int dense_assign_max();
+void launch_gb_dense_count(const int64_t*, const int64_t*, int, int64_t*,
+                           hipStream_t);
+void launch_gb_dense_assign(const int64_t*, const int64_t*, const int64_t*,
+                            int, int32_t*, int64_t*, int64_t*, hipStream_t);
+void launch_scatter_tile_prep(const int32_t*, int64_t, int, uint16_t*,
+                              int32_t*, hipStream_t);
+void launch_scatter_tile(const double*, const uint16_t*, const int32_t*,
+                         int64_t, int, double*, hipStream_t);
+void launch_gb_dense_aggregate(const int32_t*, const double*, int64_t,
+                               const int64_t*, const int64_t*, int, int64_t,
+                               double*, int64_t, int, hipStream_t);
 void launch_scatter_by_pos(const double*, const int32_t*, int64_t, double*,
                            hipStream_t);
 void launch_gb_aggregate_part(const int64_t*, const double*, const int32_t*,
@@ -235,7 +247,8 @@ std::vector<at::Tensor> gb_aggregate(at::Tensor keys, at::Tensor vals,
 std::vector<at::Tensor> gb_aggregate_partitioned(
     at::Tensor keys, at::Tensor vals, at::Tensor ops, int64_t num_parts,
     int64_t tsize, int64_t scatter_chunk, int64_t agg_chunk, int64_t nt,
-    int64_t narrow, bool record_layout, bool force_simple) {
+    int64_t narrow, bool record_layout, bool force_simple,
+    int64_t record_chunk) {
   check_gpu(keys, "keys");
   check_gpu(vals, "vals");
   TORCH_CHECK((tsize & (tsize - 1)) == 0, "tsize must be a power of 2");
@@ -298,7 +311,7 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
                            pkeys.data_ptr<int64_t>(), pvals.data_ptr<double>(),
                            (int)num_parts,
                            record_layout ? pos.data_ptr<int32_t>() : nullptr,
-                           stream);
+                           record_layout ? record_chunk : 0, stream);
   }
   // phase 3: per-partition LDS aggregation into the global table
   auto tkeys = at::full({tsize}, (int64_t)0x8000000000000000LL,
@@ -349,6 +362,202 @@ std::vector<at::Tensor> gb_aggregate_replay(at::Tensor pkeys_cached,
       agg_chunk, (int)nt, pkeys_cached.element_size() == 4 ? 1 : 0,
       (int)slots, stream);
   return {tkeys, gaggs, gcount};
+}
+
+// ---- dense replay (relational.hip "shuffle-layout reuse") ----
+
+namespace {
+void check_tile(int64_t tile) {
+  TORCH_CHECK(tile >= 512 && tile <= 8192 && (tile & (tile - 1)) == 0,
+              "tile must be a power of 2 in [512, 8192]");
+}
+void check_dense_slots(int64_t slots) {
+  TORCH_CHECK(slots == 2048 || slots == 4096 || slots == 8192,
+              "dense table slots must be 2048, 4096 or 8192");
+}
+}  // namespace
+
+// Preparation pass 1: per-partition offsets of the recorded partitioned
+// keys (re-histogrammed: same hash, same partition ids) and the number
+// of distinct keys in every partition.  A count above dense_assign_max
+// means the partition overflowed the id-assignment table.
+std::vector<at::Tensor> gb_dense_count(at::Tensor pkeys, int64_t num_parts) {
+  check_gpu(pkeys, "pkeys");
+  TORCH_CHECK(pkeys.scalar_type() == at::kLong, "pkeys must be int64");
+  TORCH_CHECK(num_parts >= 1 && num_parts <= 4096 &&
+                  (num_parts & (num_parts - 1)) == 0,
+              "num_parts must be a power of 2 <= 4096");
+  int64_t n = pkeys.numel();
+  auto stream = current_stream();
+  int shift = 64;
+  {
+    int64_t p = num_parts;
+    while (p > 1) { --shift; p >>= 1; }
+  }
+  auto hist = at::zeros({num_parts}, pkeys.options());
+  launch_gb_part_hist(pkeys.data_ptr<int64_t>(), n, shift,
+                      hist.data_ptr<int64_t>(), (int)num_parts, nullptr,
+                      stream);
+  auto offsets = at::zeros({num_parts + 1}, pkeys.options());
+  offsets.narrow(0, 1, num_parts).copy_(at::cumsum(hist, 0));
+  auto distinct = at::empty({num_parts}, pkeys.options());
+  launch_gb_dense_count(pkeys.data_ptr<int64_t>(),
+                        offsets.data_ptr<int64_t>(), (int)num_parts,
+                        distinct.data_ptr<int64_t>(), stream);
+  return {offsets, distinct};
+}
+
+// Preparation pass 2: dense group id of every partitioned row plus the
+// output keys and counts in id order.  group_base is the exclusive scan
+// of the pass-1 distinct counts ([P+1]); the caller has checked that no
+// count exceeds dense_assign_max and that n_groups < 2^31.
+std::vector<at::Tensor> gb_dense_assign(at::Tensor pkeys, at::Tensor offsets,
+                                        at::Tensor group_base,
+                                        int64_t n_groups) {
+  check_gpu(pkeys, "pkeys");
+  check_gpu(offsets, "offsets");
+  check_gpu(group_base, "group_base");
+  TORCH_CHECK(pkeys.scalar_type() == at::kLong, "pkeys must be int64");
+  TORCH_CHECK(offsets.scalar_type() == at::kLong &&
+                  group_base.scalar_type() == at::kLong,
+              "offsets/group_base must be int64");
+  int64_t num_parts = offsets.numel() - 1;
+  TORCH_CHECK(num_parts >= 1 && group_base.numel() == num_parts + 1,
+              "offsets/group_base must be [P+1]");
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  int64_t n = pkeys.numel();
+  auto gid = at::empty({n}, pkeys.options().dtype(at::kInt));
+  auto out_keys = at::empty({n_groups}, pkeys.options());
+  auto out_count = at::empty({n_groups}, pkeys.options());
+  launch_gb_dense_assign(pkeys.data_ptr<int64_t>(),
+                         offsets.data_ptr<int64_t>(),
+                         group_base.data_ptr<int64_t>(), (int)num_parts,
+                         gid.data_ptr<int32_t>(), out_keys.data_ptr<int64_t>(),
+                         out_count.data_ptr<int64_t>(), current_stream());
+  return {gid, out_keys, out_count};
+}
+
+// Preparation of the tile-coalesced scatter for a permutation `pos`:
+// (rank [n] int16 holding uint16 tile-local ranks, dst [n] int32).
+std::vector<at::Tensor> scatter_tile_prepare(at::Tensor pos, int64_t tile) {
+  check_gpu(pos, "pos");
+  TORCH_CHECK(pos.scalar_type() == at::kInt, "pos must be int32");
+  check_tile(tile);
+  int64_t n = pos.numel();
+  auto rank = at::empty({n}, pos.options().dtype(at::kShort));
+  auto dst = at::empty({n}, pos.options());
+  if (n > 0) {
+    launch_scatter_tile_prep(pos.data_ptr<int32_t>(), n, (int)tile,
+                             (uint16_t*)rank.data_ptr<int16_t>(),
+                             dst.data_ptr<int32_t>(), current_stream());
+  }
+  return {rank, dst};
+}
+
+namespace {
+void scatter_tile_into(const at::Tensor& vals, const at::Tensor& rank,
+                       const at::Tensor& dst, int64_t tile, at::Tensor& out) {
+  check_gpu(vals, "vals");
+  check_gpu(rank, "rank");
+  check_gpu(dst, "dst");
+  check_tile(tile);
+  int64_t n = dst.numel();
+  TORCH_CHECK(vals.scalar_type() == at::kDouble && vals.numel() == n,
+              "vals must be fp64 [n]");
+  TORCH_CHECK(rank.scalar_type() == at::kShort && rank.numel() == n,
+              "rank must be int16 [n]");
+  TORCH_CHECK(dst.scalar_type() == at::kInt, "dst must be int32");
+  if (n > 0) {
+    launch_scatter_tile(vals.data_ptr<double>(),
+                        (const uint16_t*)rank.data_ptr<int16_t>(),
+                        dst.data_ptr<int32_t>(), n, (int)tile,
+                        out.data_ptr<double>(), current_stream());
+  }
+}
+
+void dense_aggregate_into(const at::Tensor& gid, const at::Tensor& pvals,
+                          const at::Tensor& offsets,
+                          const at::Tensor& group_base, int64_t chunk,
+                          int64_t slots, at::Tensor& out_sum) {
+  check_gpu(gid, "gid");
+  check_gpu(pvals, "pvals");
+  check_gpu(offsets, "offsets");
+  check_gpu(group_base, "group_base");
+  check_dense_slots(slots);
+  int64_t n = gid.numel();
+  TORCH_CHECK(gid.scalar_type() == at::kInt, "gid must be int32");
+  TORCH_CHECK(pvals.scalar_type() == at::kDouble && pvals.numel() == n,
+              "pvals must be fp64 [n]");
+  TORCH_CHECK(offsets.scalar_type() == at::kLong &&
+                  group_base.scalar_type() == at::kLong &&
+                  offsets.numel() >= 2 &&
+                  group_base.numel() == offsets.numel(),
+              "offsets/group_base must be int64 [P+1]");
+  TORCH_CHECK(chunk >= 0, "chunk must be >= 0");
+  if (n > 0) {
+    launch_gb_dense_aggregate(
+        gid.data_ptr<int32_t>(), pvals.data_ptr<double>(), n,
+        offsets.data_ptr<int64_t>(), group_base.data_ptr<int64_t>(),
+        (int)(offsets.numel() - 1), out_sum.numel(),
+        out_sum.data_ptr<double>(), chunk, (int)slots, current_stream());
+  }
+}
+}  // namespace
+
+// out[pos[i]] = vals[i] through the prepared (rank, dst) tile layout
+at::Tensor scatter_tile(at::Tensor vals, at::Tensor rank, at::Tensor dst,
+                        int64_t tile) {
+  auto out = at::empty({dst.numel()}, vals.options());
+  scatter_tile_into(vals, rank, dst, tile, out);
+  return out;
+}
+
+// out_sum[g] = sum of pvals[j] over gid[j] == g, for partition-major ids
+at::Tensor gb_dense_aggregate(at::Tensor gid, at::Tensor pvals,
+                              at::Tensor offsets, at::Tensor group_base,
+                              int64_t n_groups, int64_t chunk,
+                              int64_t slots) {
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  auto out_sum = at::zeros({n_groups}, pvals.options());
+  dense_aggregate_into(gid, pvals, offsets, group_base, chunk, slots,
+                       out_sum);
+  return out_sum;
+}
+
+// One replayed step: place the fresh values (tile-coalesced when the
+// layout carries rank/dst, tile > 0; by recorded position otherwise) and
+// add them per dense group id.  Returns the [G] sums in id order.
+at::Tensor gb_replay_dense(at::Tensor vals,
+                           c10::optional<at::Tensor> rank,
+                           at::Tensor dst_or_pos, at::Tensor gid,
+                           at::Tensor offsets, at::Tensor group_base,
+                           int64_t n_groups, int64_t tile, int64_t chunk,
+                           int64_t slots) {
+  check_gpu(vals, "vals");
+  check_gpu(dst_or_pos, "dst_or_pos");
+  int64_t n = gid.numel();
+  TORCH_CHECK(vals.scalar_type() == at::kDouble && vals.numel() == n,
+              "vals must be fp64 [1, n]");
+  TORCH_CHECK(dst_or_pos.scalar_type() == at::kInt &&
+                  dst_or_pos.numel() == n,
+              "dst/pos must be int32 [n]");
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  auto pvals = at::empty({n}, vals.options());
+  if (tile > 0) {
+    TORCH_CHECK(rank.has_value(), "tile scatter needs rank");
+    scatter_tile_into(vals.view({n}), *rank, dst_or_pos, tile, pvals);
+  } else if (n > 0) {
+    launch_scatter_by_pos(vals.data_ptr<double>(),
+                          dst_or_pos.data_ptr<int32_t>(), n,
+                          pvals.data_ptr<double>(), current_stream());
+  }
+  auto out_sum = at::zeros({n_groups}, vals.options());
+  dense_aggregate_into(gid, pvals, offsets, group_base, chunk, slots,
+                       out_sum);
+  return out_sum;
 }
 
 std::vector<at::Tensor> join_build(at::Tensor keys, int64_t tsize) {
@@ -1058,7 +1267,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gb_aggregate_replay", &gb_aggregate_replay,
         "re-aggregate with a recorded shuffle layout");
   m.def("gb_aggregate_partitioned", &gb_aggregate_partitioned,
-        "partitioned (2-phase) hash group-by aggregation");
+        "partitioned (2-phase) hash group-by aggregation", py::arg("keys"),
+        py::arg("vals"), py::arg("ops"), py::arg("num_parts"),
+        py::arg("tsize"), py::arg("scatter_chunk"), py::arg("agg_chunk"),
+        py::arg("nt"), py::arg("narrow"), py::arg("record_layout"),
+        py::arg("force_simple"), py::arg("record_chunk") = 0);
+  m.def("dense_assign_max", []() { return (int64_t)dense_assign_max(); },
+        "largest per-partition distinct count the dense layout accepts");
+  m.def("gb_dense_count", &gb_dense_count,
+        "dense replay preparation: offsets + distinct keys per partition");
+  m.def("gb_dense_assign", &gb_dense_assign,
+        "dense replay preparation: group ids, output keys and counts");
+  m.def("scatter_tile_prepare", &scatter_tile_prepare,
+        "tile-coalesced scatter preparation (rank, dst) of a permutation");
+  m.def("scatter_tile", &scatter_tile, "tile-coalesced value scatter");
+  m.def("gb_dense_aggregate", &gb_dense_aggregate,
+        "sum per dense group id (LDS table per chunk)");
+  m.def("gb_replay_dense", &gb_replay_dense,
+        "replayed step: value scatter + dense aggregate");
   m.def("join_build", &join_build, "build chained hash table");
   m.def("join_emit_unique", &join_emit_unique,
         "single-pass join emit for unique build keys");

@@ -209,9 +209,14 @@ _KEY_STATS_MEMO: "Dict[Tuple[int, ...], Tuple[Any, Any]]" = {}
 _KEY_STATS_MEMO_CAP = 128
 
 # shuffle-layout reuse (Spark shuffle-reuse analog): for a repeated key
-# tensor, the partition layout (spill keys + per-row positions) is
-# recorded once and fresh values replay through it.  Two entries ~1GB
-# each at 125M rows — bound the cache tightly.
+# tensor, the partition layout is recorded once and fresh values replay
+# through it.  A plain entry caches the spill keys + per-row positions
+# (pkeys 4-8 B + pos 4 B per row).  A dense entry (single SUM over a
+# null-free fp64 column, FUGUE_GB_REPLAY_DENSE=1) caches per row the
+# dense group id (4 B) and the tile scatter's rank + destination
+# (2 B + 4 B) = 10 B/row, plus keys and counts per GROUP; pkeys and pos
+# are dropped.  Two entries ~1.25GB each at 125M rows — bound the cache
+# tightly.
 _LAYOUT_MEMO: "Dict[Tuple[int, ...], Dict[str, Any]]" = {}
 _LAYOUT_MEMO_CAP = 2
 # key tensors seen once (candidates): recording uses the slower simple
@@ -219,6 +224,62 @@ _LAYOUT_MEMO_CAP = 2
 # one-shot group-bys never pay the record cost
 _LAYOUT_SEEN: "Dict[Tuple[int, ...], Any]" = {}
 _LAYOUT_SEEN_CAP = 16
+
+
+def _replay_tile() -> int:
+    """Rows per tile of the replay value scatter (FUGUE_GB_REPLAY_TILE):
+    a power of two in [512, 8192], or 0 to replay values by recorded
+    position (the pre-tile scatter, kept for A/B).  The layout is
+    recorded with a reservation chunk equal to the tile, so the rows of
+    one (tile, partition) leave as one contiguous run."""
+    tile = int(os.environ.get("FUGUE_GB_REPLAY_TILE", "8192"))
+    if tile == 0:
+        return 0
+    if tile < 512 or tile > 8192 or tile & (tile - 1):
+        raise ValueError(
+            f"FUGUE_GB_REPLAY_TILE={tile}: expected 0 or a power of two "
+            "in [512, 8192]"
+        )
+    return tile
+
+
+def _dense_slots() -> int:
+    """LDS table slots of the dense replay aggregate
+    (FUGUE_GB_DENSE_SLOTS: 2048, 4096 or 8192; 8 B per slot)."""
+    slots = int(os.environ.get("FUGUE_GB_DENSE_SLOTS", "4096"))
+    return slots if slots in (2048, 4096, 8192) else 4096
+
+
+def _prepare_dense_layout(
+    ext: Any, pkeys: "torch.Tensor", pos: "torch.Tensor", num_parts: int,
+    tile: int,
+) -> Optional[Dict[str, Any]]:
+    """One-time preparation of the dense replay layout from the recorded
+    partitioned keys (int64) and per-row spill positions; None when it is
+    declined (a partition's distinct keys overflow the id-assignment
+    table, or G >= 2^31) and the plain replay entry must be kept.  One
+    host readback, once per key tensor."""
+    offsets, distinct = ext.gb_dense_count(pkeys, num_parts)
+    group_base = torch.zeros(
+        num_parts + 1, dtype=torch.int64, device=pkeys.device
+    )
+    torch.cumsum(distinct, 0, out=group_base[1:])
+    dmax, n_groups = torch.stack([distinct.max(), group_base[-1]]).tolist()
+    if dmax > int(ext.dense_assign_max()) or n_groups >= (1 << 31):
+        return None
+    gid, out_keys, out_count = ext.gb_dense_assign(
+        pkeys, offsets, group_base, n_groups
+    )
+    ent: Dict[str, Any] = dict(
+        dense=True, dense_hits=0, gid=gid, offsets=offsets,
+        group_base=group_base, n_groups=int(n_groups), out_keys=out_keys,
+        out_count=out_count, tile=tile,
+    )
+    if tile > 0:
+        ent["rank"], ent["dst"] = ext.scatter_tile_prepare(pos, tile)
+    else:
+        ent["rank"], ent["dst"] = None, pos
+    return ent
 
 
 def _key_stats_device(
@@ -586,8 +647,47 @@ def groupby_aggregate(
             and n < (1 << 31)
             and num_parts in (512, 1024, 2048)
         )
-        lkey = (packed.data_ptr(), n, num_parts, tsize, narrow)
+        # dense replay (FUGUE_GB_REPLAY_DENSE, default on): the zero-copy
+        # condition above plus the op.  The gate and the
+        # scatter tile are part of the memo key so an in-process A/B keeps
+        # one entry per side.
+        dense_ok = (
+            reuse
+            and os.environ.get("FUGUE_GB_REPLAY_DENSE", "1") != "0"
+            and valids is None
+            and n_aggs == 1
+            and aggs[0][1] == AGG_SUM
+            and vals.dim() == 2
+            and vals.size(0) == 1
+            and df.col(aggs[0][0]).data.dtype == torch.float64
+        )
+        tile = _replay_tile() if dense_ok else 0
+        lkey = (
+            packed.data_ptr(), n, num_parts, tsize, narrow, dense_ok, tile,
+        )
         ent = _LAYOUT_MEMO.get(lkey) if reuse else None
+        if (
+            ent is not None
+            and ent["ref"]() is not None
+            and ent.get("dense")
+        ):
+            # dense replay: groups, counts, output order and every row's
+            # group were fixed when the layout was recorded; the step is
+            # the value scatter + one LDS add per row.  The SAME cached
+            # out_keys/out_count tensors are returned every call on
+            # purpose: columns are immutable, and a stable key tensor
+            # lets the identity-memoized key stats of a downstream join
+            # hit instead of re-running.
+            out_sum = ext.gb_replay_dense(
+                vals, ent["rank"], ent["dst"], ent["gid"], ent["offsets"],
+                ent["group_base"], ent["n_groups"], ent["tile"], ag_chunk,
+                _dense_slots(),
+            )
+            ent["dense_hits"] += 1
+            return (
+                ent["out_keys"], {aggs[0][2]: out_sum}, ent["out_count"],
+                meta,
+            )
         if ent is not None and ent["ref"]() is not None:
             # replay: fresh values through the recorded layout — phase 1
             # (hist) and the key scatter are skipped entirely
@@ -615,16 +715,22 @@ def groupby_aggregate(
             tkeys, gaggs, gcount, ovf, pkeys_l, pos = (
                 ext.gb_aggregate_partitioned(
                     packed, vals, ops, num_parts, tsize, sc_chunk,
-                    ag_chunk, nt, 0, True, False
+                    ag_chunk, nt, 0, True, False, tile
                 )
             )
-            if narrow == 1:
-                pkeys_l = pkeys_l.to(torch.int32)
+            new_ent = None
+            if dense_ok:
+                new_ent = _prepare_dense_layout(
+                    ext, pkeys_l, pos, num_parts, tile
+                )
+            if new_ent is None:
+                if narrow == 1:
+                    pkeys_l = pkeys_l.to(torch.int32)
+                new_ent = dict(pkeys=pkeys_l, pos=pos, dense=False)
+            new_ent["ref"] = weakref.ref(packed)
             if len(_LAYOUT_MEMO) >= _LAYOUT_MEMO_CAP:
                 _LAYOUT_MEMO.pop(next(iter(_LAYOUT_MEMO)))
-            _LAYOUT_MEMO[lkey] = dict(
-                ref=weakref.ref(packed), pkeys=pkeys_l, pos=pos
-            )
+            _LAYOUT_MEMO[lkey] = new_ent
         else:
             tkeys, gaggs, gcount, ovf, _pk, _pos = (
                 ext.gb_aggregate_partitioned(
