@@ -20,13 +20,9 @@ CONFIGS = [
     dict(FUGUE_GB_PARTS="1024", FUGUE_GB_AGG_CHUNK="32768"),
     dict(FUGUE_GB_PARTS="2048"),
     dict(FUGUE_GB_PARTS="2048", FUGUE_GB_SCATTER_CHUNK="32768"),
-    dict(FUGUE_GB_PARTS="512", FUGUE_SC_ILP="4"),
-    dict(FUGUE_GB_PARTS="1024", FUGUE_GB_ILP="1"),
+    dict(FUGUE_GB_PARTS="512"),
 ]
-KNOBS = (
-    "FUGUE_GB_PARTS", "FUGUE_GB_AGG_CHUNK", "FUGUE_GB_SCATTER_CHUNK",
-    "FUGUE_SC_ILP", "FUGUE_GB_ILP",
-)
+KNOBS = ("FUGUE_GB_PARTS", "FUGUE_GB_AGG_CHUNK", "FUGUE_GB_SCATTER_CHUNK")
 
 
 def main() -> None:

@@ -38,7 +38,7 @@ void launch_join_build(const int64_t*, int64_t, int32_t*, int32_t*, int64_t,
                        int32_t*,
                        hipStream_t);
 void launch_gb_part_hist(const int64_t*, int64_t, int, int64_t*, int,
-                         int64_t*, hipStream_t);
+                         hipStream_t);
 void launch_reduce_cols(const double*, const bool*, const int32_t*, int,
                         int64_t, double*, int64_t*, hipStream_t);
 void launch_gb_part_scatter(const int64_t*, const double*, int, int64_t, int,
@@ -63,11 +63,11 @@ void launch_gb_aggregate_part(const int64_t*, const double*, const int32_t*,
                               double*, int64_t*, int64_t, hipStream_t);
 void launch_gb_part_scatter_staged(const int64_t*, const double*, int64_t,
                                    int, int64_t*, void*, double*, int64_t,
-                                   int, int, int*, int, hipStream_t);
+                                   int, int*, int, hipStream_t);
 void launch_gb_aggregate_part_big(const void*, const double*,
                                   const int32_t*, int64_t, int64_t*,
                                   double*, int64_t*, int64_t, int64_t,
-                                  int, int, int, hipStream_t);
+                                  int, int, hipStream_t);
 void launch_gather_cols(const uint64_t*, const uint64_t*, int, int,
                         const int64_t*, int64_t, hipStream_t);
 void launch_expr_filter(const void*, int64_t, bool*, hipStream_t);
@@ -142,6 +142,44 @@ void check_gpu(const at::Tensor& t, const char* name) {
 const bool* opt_valid_ptr(const c10::optional<at::Tensor>& v) {
   if (!v.has_value()) return nullptr;
   return v->data_ptr<bool>();
+}
+
+// ---- shared pieces of the partitioned group-by ----
+
+// partition id = mix64(key) >> part_shift(P): the top log2(P) hash bits
+int part_shift(int64_t num_parts) {
+  int shift = 64;
+  for (int64_t p = num_parts; p > 1; p >>= 1) --shift;
+  return shift;
+}
+
+// phase-3 LDS table sized for ~0.5 load at the partition granularity:
+// 512 parts -> 4096 slots, 1024 -> 2048, 2048 -> 1024
+int part_slots(int64_t num_parts) {
+  return num_parts == 1024 ? 2048 : (num_parts == 2048 ? 1024 : 4096);
+}
+
+// partition histogram of int64 `keys` as exclusive offsets [P+1]
+at::Tensor part_offsets(const at::Tensor& keys, int64_t num_parts, int shift,
+                        hipStream_t stream) {
+  auto hist = at::zeros({num_parts}, keys.options());
+  launch_gb_part_hist(keys.data_ptr<int64_t>(), keys.numel(), shift,
+                      hist.data_ptr<int64_t>(), (int)num_parts, stream);
+  auto offsets = at::zeros({num_parts + 1}, keys.options());
+  offsets.narrow(0, 1, num_parts).copy_(at::cumsum(hist, 0));
+  return offsets;
+}
+
+// empty global group table: keys at GB_EMPTY, aggregates and counts 0
+struct GroupTable {
+  at::Tensor tkeys, gaggs, gcount;
+};
+GroupTable empty_group_table(int64_t n_aggs, int64_t tsize,
+                             const at::Tensor& vals) {
+  auto kopts = vals.options().dtype(at::kLong);
+  return {at::full({tsize}, (int64_t)0x8000000000000000LL, kopts),
+          at::zeros({n_aggs, tsize}, vals.options()),
+          at::zeros({tsize}, kopts)};
 }
 
 }  // namespace
@@ -225,47 +263,37 @@ std::vector<at::Tensor> gb_aggregate(at::Tensor keys, at::Tensor vals,
   int64_t n = keys.numel();
   int n_aggs = (int)vals.size(0);
   TORCH_CHECK(vals.dim() == 2 && vals.size(1) == n, "vals must be [A, n]");
-  auto tkeys = at::full({tsize}, (int64_t)0x8000000000000000LL,
-                        keys.options());
+  auto t = empty_group_table(n_aggs, tsize, vals);
   // init aggs to op-appropriate identity: sum/count -> 0; min -> +inf; max -> -inf
-  auto gaggs = at::zeros({n_aggs, tsize}, vals.options());
   auto ops_cpu = ops.to(at::kCPU);
   for (int a = 0; a < n_aggs; ++a) {
     int op = ops_cpu[a].item<int32_t>();
-    if (op == 1) gaggs[a].fill_(std::numeric_limits<double>::infinity());
-    if (op == 2) gaggs[a].fill_(-std::numeric_limits<double>::infinity());
+    if (op == 1) t.gaggs[a].fill_(std::numeric_limits<double>::infinity());
+    if (op == 2) t.gaggs[a].fill_(-std::numeric_limits<double>::infinity());
   }
-  auto gcount = at::zeros({tsize}, keys.options());
   launch_gb_aggregate(keys.data_ptr<int64_t>(), vals.data_ptr<double>(),
                       opt_valid_ptr(valids), ops.data_ptr<int32_t>(), n_aggs,
-                      n, tkeys.data_ptr<int64_t>(), gaggs.data_ptr<double>(),
-                      gcount.data_ptr<int64_t>(), tsize, use_lds ? 1 : 0,
+                      n, t.tkeys.data_ptr<int64_t>(),
+                      t.gaggs.data_ptr<double>(),
+                      t.gcount.data_ptr<int64_t>(), tsize, use_lds ? 1 : 0,
                       current_stream());
-  return {tkeys, gaggs, gcount};
+  return {t.tkeys, t.gaggs, t.gcount};
 }
 
 std::vector<at::Tensor> gb_aggregate_partitioned(
     at::Tensor keys, at::Tensor vals, at::Tensor ops, int64_t num_parts,
-    int64_t tsize, int64_t scatter_chunk, int64_t agg_chunk, int64_t nt,
-    int64_t narrow, bool record_layout, bool force_simple,
-    int64_t record_chunk) {
+    int64_t tsize, int64_t scatter_chunk, int64_t agg_chunk, int64_t narrow,
+    bool record_layout, bool force_simple, int64_t record_chunk) {
   check_gpu(keys, "keys");
   check_gpu(vals, "vals");
   TORCH_CHECK((tsize & (tsize - 1)) == 0, "tsize must be a power of 2");
   TORCH_CHECK((num_parts & (num_parts - 1)) == 0,
               "num_parts must be a power of 2");
+  TORCH_CHECK(num_parts <= 4096, "num_parts must be <= 4096");
   int64_t n = keys.numel();
   int n_aggs = (int)vals.size(0);
   auto stream = current_stream();
-  int shift = 64;
-  {
-    int64_t p = num_parts;
-    while (p > 1) { --shift; p >>= 1; }
-  }
-  // phase 1: histogram + scan (also reduces key min/max when the
-  // caller asks for narrow auto-detection: narrow < 0)
-  auto hist = at::zeros({num_parts}, keys.options());
-  TORCH_CHECK(num_parts <= 4096, "num_parts must be <= 4096");
+  int shift = part_shift(num_parts);
   bool staged =
       (n_aggs == 1 &&
        (num_parts == 512 || num_parts == 1024 || num_parts == 2048));
@@ -274,19 +302,13 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
   // spill format (narrow keys done by the caller)
   record_layout = record_layout && n_aggs == 1 && n < (int64_t(1) << 31);
   if (record_layout || force_simple) staged = false;
-  // phase-3 LDS table sized for ~0.5 load at the partition granularity:
-  // 512 parts -> 4096 slots, 1024 -> 2048, 2048 -> 1024
-  int slots = num_parts == 1024 ? 2048 : (num_parts == 2048 ? 1024 : 4096);
   // narrow < 0 = speculative: run the int32 path with an in-kernel
   // overflow flag; the CALLER checks the returned flag at its existing
   // sync point and re-runs wide if set (no mid-pipeline sync here)
   bool speculative = staged && narrow < 0;
   if (speculative) narrow = 1;
-  launch_gb_part_hist(keys.data_ptr<int64_t>(), n, shift,
-                      hist.data_ptr<int64_t>(), (int)num_parts, nullptr,
-                      stream);
-  auto offsets = at::zeros({num_parts + 1}, keys.options());
-  offsets.narrow(0, 1, num_parts).copy_(at::cumsum(hist, 0));
+  // phase 1: histogram + scan
+  auto offsets = part_offsets(keys, num_parts, shift, stream);
   auto cursor = offsets.narrow(0, 0, num_parts).clone();
   // phase 2: scatter into partitioned order
   bool use_narrow = staged && narrow > 0;
@@ -301,8 +323,7 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
     launch_gb_part_scatter_staged(
         keys.data_ptr<int64_t>(), vals.data_ptr<double>(), n, shift,
         cursor.data_ptr<int64_t>(), pkeys.data_ptr(),
-        pvals.data_ptr<double>(), scatter_chunk, (int)nt,
-        use_narrow ? 1 : 0,
+        pvals.data_ptr<double>(), scatter_chunk, use_narrow ? 1 : 0,
         (use_narrow && speculative) ? ovf.data_ptr<int32_t>() : nullptr,
         (int)num_parts, stream);
   } else {
@@ -314,24 +335,21 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
                            record_layout ? record_chunk : 0, stream);
   }
   // phase 3: per-partition LDS aggregation into the global table
-  auto tkeys = at::full({tsize}, (int64_t)0x8000000000000000LL,
-                        keys.options());
-  auto gaggs = at::zeros({n_aggs, tsize}, vals.options());
-  auto gcount = at::zeros({tsize}, keys.options());
+  auto t = empty_group_table(n_aggs, tsize, vals);
   if (staged) {
     launch_gb_aggregate_part_big(
         pkeys.data_ptr(), pvals.data_ptr<double>(),
-        ops.data_ptr<int32_t>(), n, tkeys.data_ptr<int64_t>(),
-        gaggs.data_ptr<double>(), gcount.data_ptr<int64_t>(), tsize,
-        agg_chunk, (int)nt, use_narrow ? 1 : 0, slots, stream);
+        ops.data_ptr<int32_t>(), n, t.tkeys.data_ptr<int64_t>(),
+        t.gaggs.data_ptr<double>(), t.gcount.data_ptr<int64_t>(), tsize,
+        agg_chunk, use_narrow ? 1 : 0, part_slots(num_parts), stream);
   } else {
     launch_gb_aggregate_part(
         pkeys.data_ptr<int64_t>(), pvals.data_ptr<double>(),
         ops.data_ptr<int32_t>(), n_aggs, n, offsets.data_ptr<int64_t>(),
-        num_parts, tkeys.data_ptr<int64_t>(), gaggs.data_ptr<double>(),
-        gcount.data_ptr<int64_t>(), tsize, stream);
+        num_parts, t.tkeys.data_ptr<int64_t>(), t.gaggs.data_ptr<double>(),
+        t.gcount.data_ptr<int64_t>(), tsize, stream);
   }
-  return {tkeys, gaggs, gcount, ovf, pkeys, pos};
+  return {t.tkeys, t.gaggs, t.gcount, ovf, pkeys, pos};
 }
 
 // Phase 2+3 only, with a recorded layout: place the fresh values at
@@ -339,9 +357,9 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
 // partitioned keys (phase 1 + key scatter skipped entirely).
 std::vector<at::Tensor> gb_aggregate_replay(at::Tensor pkeys_cached,
                                             at::Tensor pos, at::Tensor vals,
-                                            at::Tensor ops, int64_t tsize,
-                                            int64_t agg_chunk, int64_t nt,
-                                            int64_t slots) {
+                                            at::Tensor ops, int64_t num_parts,
+                                            int64_t tsize,
+                                            int64_t agg_chunk) {
   check_gpu(pkeys_cached, "pkeys");
   check_gpu(pos, "pos");
   check_gpu(vals, "vals");
@@ -351,17 +369,14 @@ std::vector<at::Tensor> gb_aggregate_replay(at::Tensor pkeys_cached,
   auto pvals = at::empty({1, n}, vals.options());
   launch_scatter_by_pos(vals.data_ptr<double>(), pos.data_ptr<int32_t>(), n,
                         pvals.data_ptr<double>(), stream);
-  auto tkeys = at::full({tsize}, (int64_t)0x8000000000000000LL,
-                        pos.options().dtype(at::kLong));
-  auto gaggs = at::zeros({1, tsize}, vals.options());
-  auto gcount = at::zeros({tsize}, pos.options().dtype(at::kLong));
+  auto t = empty_group_table(1, tsize, vals);
   launch_gb_aggregate_part_big(
       pkeys_cached.data_ptr(), pvals.data_ptr<double>(),
-      ops.data_ptr<int32_t>(), n, tkeys.data_ptr<int64_t>(),
-      gaggs.data_ptr<double>(), gcount.data_ptr<int64_t>(), tsize,
-      agg_chunk, (int)nt, pkeys_cached.element_size() == 4 ? 1 : 0,
-      (int)slots, stream);
-  return {tkeys, gaggs, gcount};
+      ops.data_ptr<int32_t>(), n, t.tkeys.data_ptr<int64_t>(),
+      t.gaggs.data_ptr<double>(), t.gcount.data_ptr<int64_t>(), tsize,
+      agg_chunk, pkeys_cached.element_size() == 4 ? 1 : 0,
+      part_slots(num_parts), stream);
+  return {t.tkeys, t.gaggs, t.gcount};
 }
 
 // ---- dense replay (relational.hip "shuffle-layout reuse") ----
@@ -387,19 +402,9 @@ std::vector<at::Tensor> gb_dense_count(at::Tensor pkeys, int64_t num_parts) {
   TORCH_CHECK(num_parts >= 1 && num_parts <= 4096 &&
                   (num_parts & (num_parts - 1)) == 0,
               "num_parts must be a power of 2 <= 4096");
-  int64_t n = pkeys.numel();
   auto stream = current_stream();
-  int shift = 64;
-  {
-    int64_t p = num_parts;
-    while (p > 1) { --shift; p >>= 1; }
-  }
-  auto hist = at::zeros({num_parts}, pkeys.options());
-  launch_gb_part_hist(pkeys.data_ptr<int64_t>(), n, shift,
-                      hist.data_ptr<int64_t>(), (int)num_parts, nullptr,
-                      stream);
-  auto offsets = at::zeros({num_parts + 1}, pkeys.options());
-  offsets.narrow(0, 1, num_parts).copy_(at::cumsum(hist, 0));
+  auto offsets =
+      part_offsets(pkeys, num_parts, part_shift(num_parts), stream);
   auto distinct = at::empty({num_parts}, pkeys.options());
   launch_gb_dense_count(pkeys.data_ptr<int64_t>(),
                         offsets.data_ptr<int64_t>(), (int)num_parts,
@@ -526,33 +531,36 @@ at::Tensor gb_dense_aggregate(at::Tensor gid, at::Tensor pvals,
   return out_sum;
 }
 
-// One replayed step: place the fresh values (tile-coalesced when the
-// layout carries rank/dst, tile > 0; by recorded position otherwise) and
-// add them per dense group id.  Returns the [G] sums in id order.
-at::Tensor gb_replay_dense(at::Tensor vals,
-                           c10::optional<at::Tensor> rank,
-                           at::Tensor dst_or_pos, at::Tensor gid,
+// One replayed step: place the fresh values and add them per dense
+// group id.  The layout carries either (rank, dst) for the
+// tile-coalesced scatter or the recorded positions `pos`.  Returns the
+// [G] sums in id order.
+at::Tensor gb_replay_dense(at::Tensor vals, at::Tensor gid,
                            at::Tensor offsets, at::Tensor group_base,
-                           int64_t n_groups, int64_t tile, int64_t chunk,
-                           int64_t slots) {
+                           int64_t n_groups, int64_t chunk, int64_t slots,
+                           int64_t tile, c10::optional<at::Tensor> rank,
+                           c10::optional<at::Tensor> dst,
+                           c10::optional<at::Tensor> pos) {
   check_gpu(vals, "vals");
-  check_gpu(dst_or_pos, "dst_or_pos");
   int64_t n = gid.numel();
   TORCH_CHECK(vals.scalar_type() == at::kDouble && vals.numel() == n,
               "vals must be fp64 [1, n]");
-  TORCH_CHECK(dst_or_pos.scalar_type() == at::kInt &&
-                  dst_or_pos.numel() == n,
-              "dst/pos must be int32 [n]");
   TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
               "n_groups must fit int32");
+  TORCH_CHECK(pos.has_value() != (rank.has_value() && dst.has_value()),
+              "pass either pos or rank and dst");
   auto pvals = at::empty({n}, vals.options());
-  if (tile > 0) {
-    TORCH_CHECK(rank.has_value(), "tile scatter needs rank");
-    scatter_tile_into(vals.view({n}), *rank, dst_or_pos, tile, pvals);
-  } else if (n > 0) {
-    launch_scatter_by_pos(vals.data_ptr<double>(),
-                          dst_or_pos.data_ptr<int32_t>(), n,
-                          pvals.data_ptr<double>(), current_stream());
+  if (pos.has_value()) {
+    check_gpu(*pos, "pos");
+    TORCH_CHECK(pos->scalar_type() == at::kInt && pos->numel() == n,
+                "pos must be int32 [n]");
+    if (n > 0) {
+      launch_scatter_by_pos(vals.data_ptr<double>(), pos->data_ptr<int32_t>(),
+                            n, pvals.data_ptr<double>(), current_stream());
+    }
+  } else {
+    TORCH_CHECK(dst->numel() == n, "dst must be int32 [n]");
+    scatter_tile_into(vals.view({n}), *rank, *dst, tile, pvals);
   }
   auto out_sum = at::zeros({n_groups}, vals.options());
   dense_aggregate_into(gid, pvals, offsets, group_base, chunk, slots,
@@ -1263,28 +1271,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bucket_histogram", &bucket_histogram, "bucket histogram");
   m.def("bucket_scatter", &bucket_scatter,
         "scatter row indices into bucket-contiguous order");
-  m.def("gb_aggregate", &gb_aggregate, "hash group-by aggregation");
+  m.def("gb_aggregate", &gb_aggregate, "hash group-by aggregation",
+        py::arg("keys"), py::arg("vals"), py::arg("valids"), py::arg("ops"),
+        py::arg("tsize"), py::arg("use_lds"));
   m.def("gb_aggregate_replay", &gb_aggregate_replay,
-        "re-aggregate with a recorded shuffle layout");
+        "re-aggregate with a recorded shuffle layout", py::arg("pkeys"),
+        py::arg("pos"), py::arg("vals"), py::arg("ops"),
+        py::arg("num_parts"), py::arg("tsize"), py::arg("agg_chunk"));
   m.def("gb_aggregate_partitioned", &gb_aggregate_partitioned,
         "partitioned (2-phase) hash group-by aggregation", py::arg("keys"),
         py::arg("vals"), py::arg("ops"), py::arg("num_parts"),
         py::arg("tsize"), py::arg("scatter_chunk"), py::arg("agg_chunk"),
-        py::arg("nt"), py::arg("narrow"), py::arg("record_layout"),
+        py::arg("narrow"), py::arg("record_layout"),
         py::arg("force_simple"), py::arg("record_chunk") = 0);
   m.def("dense_assign_max", []() { return (int64_t)dense_assign_max(); },
         "largest per-partition distinct count the dense layout accepts");
   m.def("gb_dense_count", &gb_dense_count,
-        "dense replay preparation: offsets + distinct keys per partition");
+        "dense replay preparation: offsets + distinct keys per partition",
+        py::arg("pkeys"), py::arg("num_parts"));
   m.def("gb_dense_assign", &gb_dense_assign,
-        "dense replay preparation: group ids, output keys and counts");
+        "dense replay preparation: group ids, output keys and counts",
+        py::arg("pkeys"), py::arg("offsets"), py::arg("group_base"),
+        py::arg("n_groups"));
   m.def("scatter_tile_prepare", &scatter_tile_prepare,
         "tile-coalesced scatter preparation (rank, dst) of a permutation");
   m.def("scatter_tile", &scatter_tile, "tile-coalesced value scatter");
   m.def("gb_dense_aggregate", &gb_dense_aggregate,
-        "sum per dense group id (LDS table per chunk)");
+        "sum per dense group id (LDS table per chunk)", py::arg("gid"),
+        py::arg("pvals"), py::arg("offsets"), py::arg("group_base"),
+        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"));
   m.def("gb_replay_dense", &gb_replay_dense,
-        "replayed step: value scatter + dense aggregate");
+        "replayed step: value scatter + dense aggregate", py::arg("vals"),
+        py::arg("gid"), py::arg("offsets"), py::arg("group_base"),
+        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"),
+        py::arg("tile") = 0, py::arg("rank") = py::none(),
+        py::arg("dst") = py::none(), py::arg("pos") = py::none());
   m.def("join_build", &join_build, "build chained hash table");
   m.def("join_emit_unique", &join_emit_unique,
         "single-pass join emit for unique build keys");

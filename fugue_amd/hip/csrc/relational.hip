@@ -48,21 +48,6 @@ __device__ __forceinline__ uint64_t hash_combine(uint64_t h, uint64_t v) {
   return mix64(h ^ (v + 0x9e3779b97f4a7c15ULL + (h << 6) + (h >> 2)));
 }
 
-// streaming (nontemporal) access helpers: single-use data bypasses L2/
-// MALL so cached lines survive for data that IS reused (guide §6 G13)
-template <bool NT, typename T>
-__device__ __forceinline__ T stream_ld(const T* p) {
-  return NT ? __builtin_nontemporal_load(p) : *p;
-}
-template <bool NT, typename T>
-__device__ __forceinline__ void stream_st(T* p, T v) {
-  if (NT) {
-    __builtin_nontemporal_store(v, p);
-  } else {
-    *p = v;
-  }
-}
-
 // ------------------------------------------------------------------ //
 // hashing: combine one column into the running row-hash               //
 // ------------------------------------------------------------------ //
@@ -454,18 +439,14 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_lds_kernel(
 
 #define PART_MAX 4096
 
-// LDS-privatized histogram (global atomics only on the per-block flush);
-// optionally also reduces the key min/max (wave shuffle + one device
-// atomic per wave) for the narrow-intermediate auto-detection
+// LDS-privatized histogram (global atomics only on the per-block flush)
 __global__ __launch_bounds__(BLOCK) void gb_part_hist_kernel(
     const int64_t* __restrict__ keys, int64_t n, int shift,
-    int64_t* __restrict__ hist, int num_parts,
-    int64_t* __restrict__ minmax /* [2]={min,max}, may be null */) {
+    int64_t* __restrict__ hist, int num_parts) {
   __shared__ int lhist[PART_MAX];
   for (int i = threadIdx.x; i < num_parts; i += blockDim.x) lhist[i] = 0;
   __syncthreads();
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t kmin = INT64_MAX, kmax = INT64_MIN;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + stride < n; i += 2 * stride) {
     int64_t k1 = keys[i];
@@ -474,34 +455,16 @@ __global__ __launch_bounds__(BLOCK) void gb_part_hist_kernel(
     int p2 = (int)(mix64((uint64_t)k2) >> shift);
     atomicAdd(&lhist[p1], 1);
     atomicAdd(&lhist[p2], 1);
-    if (k1 < kmin) kmin = k1;
-    if (k1 > kmax) kmax = k1;
-    if (k2 < kmin) kmin = k2;
-    if (k2 > kmax) kmax = k2;
   }
   for (; i < n; i += stride) {
     int64_t k = keys[i];
     int p = (int)(mix64((uint64_t)k) >> shift);
     atomicAdd(&lhist[p], 1);
-    if (k < kmin) kmin = k;
-    if (k > kmax) kmax = k;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < num_parts; i += blockDim.x) {
     if (lhist[i] > 0)
       atomicAdd((unsigned long long*)&hist[i], (unsigned long long)lhist[i]);
-  }
-  if (minmax != nullptr && kmin <= kmax) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
-      int64_t omin = __shfl_down(kmin, off, WAVE);
-      int64_t omax = __shfl_down(kmax, off, WAVE);
-      if (omin < kmin) kmin = omin;
-      if (omax > kmax) kmax = omax;
-    }
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-      atomicMin((long long*)&minmax[0], (long long)kmin);
-      atomicMax((long long*)&minmax[1], (long long)kmax);
-    }
   }
 }
 
@@ -624,141 +587,18 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_kernel(
   }
 }
 
-// LDS write-staged scatter: stage the first STAGE_E rows of each
-// partition per chunk in LDS and flush them as contiguous runs, so the
-// bulk of the scattered writes leave the CU coalesced instead of as
-// isolated 8B transactions.  Overflow rows (partition skew beyond
-// STAGE_E within a chunk) are written directly.  Single-agg-column
-// variant (the common case after the COUNT-from-rowcount optimization).
-#define STAGE_P 512
-#define STAGE_E 8
-
-template <bool NT, typename KT>
-__global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel(
-    const int64_t* __restrict__ keys,
-    const double* __restrict__ vals,   // [1, n]
-    int64_t n, int shift,
-    int64_t* __restrict__ cursor,
-    KT* __restrict__ out_keys,
-    double* __restrict__ out_vals,
-    int64_t chunk,
-    int* __restrict__ ovf /* set when a key overflows KT; may be null */) {
-  __shared__ int lhist[STAGE_P];
-  __shared__ int64_t lbase[STAGE_P];
-  __shared__ int lcnt[STAGE_P];
-  __shared__ KT skey[STAGE_P * STAGE_E];
-  __shared__ double sval[STAGE_P * STAGE_E];
-  for (int64_t start = (int64_t)blockIdx.x * chunk; start < n;
-       start += (int64_t)gridDim.x * chunk) {
-    int64_t end = start + chunk;
-    if (end > n) end = n;
-    for (int i = threadIdx.x; i < STAGE_P; i += blockDim.x) {
-      lhist[i] = 0;
-      lcnt[i] = 0;
-    }
-    __syncthreads();
-    {
-      int64_t i = start + threadIdx.x;
-      for (; i + blockDim.x < end; i += 2 * (int64_t)blockDim.x) {
-        int64_t k1 = keys[i];
-        int64_t k2 = keys[i + blockDim.x];
-        int p1 = (int)(mix64((uint64_t)k1) >> shift);
-        int p2 = (int)(mix64((uint64_t)k2) >> shift);
-        atomicAdd(&lhist[p1], 1);
-        atomicAdd(&lhist[p2], 1);
-      }
-      for (; i < end; i += blockDim.x) {
-        int p = (int)(mix64((uint64_t)keys[i]) >> shift);
-        atomicAdd(&lhist[p], 1);
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < STAGE_P; i += blockDim.x) {
-      int c = lhist[i];
-      lbase[i] =
-          c > 0
-              ? (int64_t)atomicAdd((unsigned long long*)&cursor[i],
-                                   (unsigned long long)c)
-              : 0;
-    }
-    __syncthreads();
-    {
-      int64_t i = start + threadIdx.x;
-      for (; i + blockDim.x < end; i += 2 * (int64_t)blockDim.x) {
-        int64_t i2 = i + blockDim.x;
-        int64_t k1 = keys[i];
-        int64_t k2 = keys[i2];
-        if constexpr (sizeof(KT) == 4) {
-          if (ovf != nullptr && ((uint64_t)k1 >= (1ULL << 31) ||
-                                 (uint64_t)k2 >= (1ULL << 31))) {
-            atomicOr(ovf, 1);
-          }
-        }
-        int p1 = (int)(mix64((uint64_t)k1) >> shift);
-        int p2 = (int)(mix64((uint64_t)k2) >> shift);
-        double v1 = stream_ld<NT>(&vals[i]);
-        double v2 = stream_ld<NT>(&vals[i2]);
-        int pos1 = atomicAdd(&lcnt[p1], 1);
-        int pos2 = atomicAdd(&lcnt[p2], 1);
-        if (pos1 < STAGE_E) {
-          skey[p1 * STAGE_E + pos1] = (KT)k1;
-          sval[p1 * STAGE_E + pos1] = v1;
-        } else {
-          int64_t gpos = lbase[p1] + pos1;
-          stream_st<NT>(&out_keys[gpos], (KT)k1);
-          stream_st<NT>(&out_vals[gpos], v1);
-        }
-        if (pos2 < STAGE_E) {
-          skey[p2 * STAGE_E + pos2] = (KT)k2;
-          sval[p2 * STAGE_E + pos2] = v2;
-        } else {
-          int64_t gpos = lbase[p2] + pos2;
-          stream_st<NT>(&out_keys[gpos], (KT)k2);
-          stream_st<NT>(&out_vals[gpos], v2);
-        }
-      }
-      for (; i < end; i += blockDim.x) {
-        int64_t key = keys[i];
-        if constexpr (sizeof(KT) == 4) {
-          if (ovf != nullptr && (uint64_t)key >= (1ULL << 31)) {
-            atomicOr(ovf, 1);
-          }
-        }
-        int p = (int)(mix64((uint64_t)key) >> shift);
-        int pos = atomicAdd(&lcnt[p], 1);
-        double v = stream_ld<NT>(&vals[i]);
-        if (pos < STAGE_E) {
-          skey[p * STAGE_E + pos] = (KT)key;
-          sval[p * STAGE_E + pos] = v;
-        } else {
-          int64_t gpos = lbase[p] + pos;
-          stream_st<NT>(&out_keys[gpos], (KT)key);
-          stream_st<NT>(&out_vals[gpos], v);
-        }
-      }
-    }
-    __syncthreads();
-    // flush staged entries as contiguous runs
-    for (int t = threadIdx.x; t < STAGE_P * STAGE_E; t += blockDim.x) {
-      int p = t / STAGE_E;
-      int e = t % STAGE_E;
-      int c = lcnt[p];
-      if (e < c && e < STAGE_E) {
-        int64_t gpos = lbase[p] + e;
-        stream_st<NT>(&out_keys[gpos], skey[t]);
-        stream_st<NT>(&out_vals[gpos], sval[t]);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ILP-4 variant of the staged scatter row loop (FUGUE_SC_ILP=4): four
+// LDS write-staged scatter: stage the first E rows of each partition
+// per chunk in LDS and flush them as contiguous runs, so the bulk of
+// the scattered writes leave the CU coalesced instead of as isolated 8B
+// transactions.  Overflow rows (partition skew beyond E within a chunk)
+// are written directly.  Single-agg-column variant (the common case
+// after the COUNT-from-rowcount optimization).  The row loop keeps four
 // key loads / hashes / value loads in flight before the LDS cursor
-// atomics, same staging scheme.  Templated on the partition count P and
-// staging depth E so occupancy/granularity variants (512/8, 1024/4,
-// 2048/2) can be A/B-tested at runtime (FUGUE_GB_PARTS).
-template <bool NT, typename KT, int P, int E>
+// atomics (the ILP-2 loop it replaced is in profiles/NOTES.md).
+// Templated on the partition count P and staging depth E so the
+// occupancy/granularity variants (512/8, 1024/4, 2048/2) can be
+// A/B-tested at runtime (FUGUE_GB_PARTS).
+template <typename KT, int P, int E>
 __global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel_v4(
     const int64_t* __restrict__ keys,
     const double* __restrict__ vals,
@@ -827,7 +667,7 @@ __global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel_v4(
         for (int u = 0; u < 4; ++u)
           p[u] = (int)(mix64((uint64_t)k[u]) >> shift);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = stream_ld<NT>(&vals[i + u * stride]);
+        for (int u = 0; u < 4; ++u) v[u] = vals[i + u * stride];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           int pos = atomicAdd(&lcnt[p[u]], 1);
@@ -836,8 +676,8 @@ __global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel_v4(
             sval[p[u] * E + pos] = v[u];
           } else {
             int64_t gpos = lbase[p[u]] + pos;
-            stream_st<NT>(&out_keys[gpos], (KT)k[u]);
-            stream_st<NT>(&out_vals[gpos], v[u]);
+            out_keys[gpos] = (KT)k[u];
+            out_vals[gpos] = v[u];
           }
         }
       }
@@ -850,14 +690,14 @@ __global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel_v4(
         }
         int p = (int)(mix64((uint64_t)key) >> shift);
         int pos = atomicAdd(&lcnt[p], 1);
-        double v = stream_ld<NT>(&vals[i]);
+        double v = vals[i];
         if (pos < E) {
           skey[p * E + pos] = (KT)key;
           sval[p * E + pos] = v;
         } else {
           int64_t gpos = lbase[p] + pos;
-          stream_st<NT>(&out_keys[gpos], (KT)key);
-          stream_st<NT>(&out_vals[gpos], v);
+          out_keys[gpos] = (KT)key;
+          out_vals[gpos] = v;
         }
       }
     }
@@ -868,8 +708,8 @@ __global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel_v4(
       int c = lcnt[p];
       if (e < c && e < E) {
         int64_t gpos = lbase[p] + e;
-        stream_st<NT>(&out_keys[gpos], skey[t]);
-        stream_st<NT>(&out_vals[gpos], sval[t]);
+        out_keys[gpos] = skey[t];
+        out_vals[gpos] = sval[t];
       }
     }
     __syncthreads();
@@ -882,7 +722,6 @@ __global__ __launch_bounds__(BLOCK) void gb_part_scatter_staged_kernel_v4(
 // correctness (the LDS table just absorbs duplicates; flushes are
 // atomic).  Chunk-striding restores full grid parallelism regardless of
 // the partition count.  4096 slots / 80KB LDS → 2 blocks/CU.
-#define LDS_SLOTS_BIG 4096
 #define AGG_CHUNK (BLOCK * 128)  // 32768 rows per chunk (sweep-tuned)
 
 // empty-slot sentinel for the LDS table: int64 path uses GB_EMPTY;
@@ -936,91 +775,11 @@ __device__ __forceinline__ void gb_lds_upsert(
   }
 }
 
-template <bool NT, typename KT>
-__global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel(
-    const KT* __restrict__ part_keys,
-    const double* __restrict__ part_vals,  // [1, n]
-    const int32_t* __restrict__ ops,
-    int64_t n,
-    int64_t* __restrict__ tkeys,
-    double* __restrict__ gaggs,
-    int64_t* __restrict__ gcount,
-    int64_t tsize, int64_t chunk) {
-  __shared__ KT lkeys[LDS_SLOTS_BIG];
-  __shared__ double laggs[LDS_SLOTS_BIG];
-  __shared__ int lcount[LDS_SLOTS_BIG];
-  const KT EMPTY = lds_empty<KT>();
-  bool is_count = ops[0] == 3;
-  for (int64_t start = (int64_t)blockIdx.x * chunk; start < n;
-       start += (int64_t)gridDim.x * chunk) {
-    int64_t end = start + chunk;
-    if (end > n) end = n;
-    for (int i = threadIdx.x; i < LDS_SLOTS_BIG; i += blockDim.x) {
-      lkeys[i] = EMPTY;
-      lcount[i] = 0;
-      laggs[i] = 0.0;
-    }
-    __syncthreads();
-    // paired (ILP-2) row processing: two independent key loads, hash
-    // computations and first-slot LDS reads in flight per iteration —
-    // hides LDS latency at the low occupancy (2 blocks/CU) this
-    // kernel's 80KB LDS footprint allows
-    int64_t i = start + threadIdx.x;
-    for (; i + blockDim.x < end; i += 2 * (int64_t)blockDim.x) {
-      int64_t i2 = i + blockDim.x;
-      KT k1 = stream_ld<NT>(&part_keys[i]);
-      KT k2 = stream_ld<NT>(&part_keys[i2]);
-      int s1 = (int)(mix64((uint64_t)(int64_t)k1) & (LDS_SLOTS_BIG - 1));
-      int s2 = (int)(mix64((uint64_t)(int64_t)k2) & (LDS_SLOTS_BIG - 1));
-      KT c1 = lkeys[s1];
-      KT c2 = lkeys[s2];
-      double v1 = is_count ? 1.0 : stream_ld<NT>(&part_vals[i]);
-      double v2 = is_count ? 1.0 : stream_ld<NT>(&part_vals[i2]);
-      if (c1 == k1) {
-        atomicAdd(&lcount[s1], 1);
-        atomicAdd(&laggs[s1], v1);
-      } else {
-        gb_lds_upsert<LDS_SLOTS_BIG, KT>(k1, v1, s1, EMPTY, lkeys, laggs, lcount, tkeys,
-                          gaggs, gcount, tsize);
-      }
-      if (c2 == k2) {
-        atomicAdd(&lcount[s2], 1);
-        atomicAdd(&laggs[s2], v2);
-      } else {
-        gb_lds_upsert<LDS_SLOTS_BIG, KT>(k2, v2, s2, EMPTY, lkeys, laggs, lcount, tkeys,
-                          gaggs, gcount, tsize);
-      }
-    }
-    for (; i < end; i += blockDim.x) {
-      KT key = stream_ld<NT>(&part_keys[i]);
-      int slot = (int)(mix64((uint64_t)(int64_t)key) & (LDS_SLOTS_BIG - 1));
-      double v = is_count ? 1.0 : stream_ld<NT>(&part_vals[i]);
-      KT cur = lkeys[slot];
-      if (cur == key) {
-        atomicAdd(&lcount[slot], 1);
-        atomicAdd(&laggs[slot], v);
-      } else {
-        gb_lds_upsert<LDS_SLOTS_BIG, KT>(key, v, slot, EMPTY, lkeys, laggs, lcount, tkeys,
-                          gaggs, gcount, tsize);
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < LDS_SLOTS_BIG; i += blockDim.x) {
-      KT key = lkeys[i];
-      if (key == EMPTY) continue;
-      int64_t gslot = gb_probe_insert((int64_t)key, tkeys, tsize);
-      atomicAdd((unsigned long long*)&gcount[gslot],
-                (unsigned long long)lcount[i]);
-      atomicAdd(&gaggs[gslot], laggs[i]);
-    }
-    __syncthreads();
-  }
-}
-
-// ILP-4 row loop variant (FUGUE_GB_ILP=4): four independent key loads /
-// hashes / first-slot LDS reads in flight per iteration — deeper
-// latency hiding at the 2-blocks/CU occupancy this kernel runs at
-template <bool NT, typename KT, int SLOTS>
+// ILP-4 row loop: four independent key loads / hashes / first-slot LDS
+// reads in flight per iteration — deeper latency hiding at the
+// 2-blocks/CU occupancy the 4096-slot table runs at (the ILP-1/ILP-2
+// loops it replaced are in profiles/NOTES.md)
+template <typename KT, int SLOTS>
 __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel_v4(
     const KT* __restrict__ part_keys,
     const double* __restrict__ part_vals,
@@ -1053,7 +812,7 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel_v4(
       KT c[4];
       double v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) k[u] = stream_ld<NT>(&part_keys[i + u * stride]);
+      for (int u = 0; u < 4; ++u) k[u] = part_keys[i + u * stride];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         s[u] = (int)(mix64((uint64_t)(int64_t)k[u]) & (SLOTS - 1));
@@ -1061,7 +820,7 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel_v4(
       for (int u = 0; u < 4; ++u) c[u] = lkeys[s[u]];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        v[u] = is_count ? 1.0 : stream_ld<NT>(&part_vals[i + u * stride]);
+        v[u] = is_count ? 1.0 : part_vals[i + u * stride];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (c[u] == k[u]) {
@@ -1074,9 +833,9 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel_v4(
       }
     }
     for (; i < end; i += stride) {
-      KT key = stream_ld<NT>(&part_keys[i]);
+      KT key = part_keys[i];
       int slot = (int)(mix64((uint64_t)(int64_t)key) & (SLOTS - 1));
-      double v = is_count ? 1.0 : stream_ld<NT>(&part_vals[i]);
+      double v = is_count ? 1.0 : part_vals[i];
       KT cur = lkeys[slot];
       if (cur == key) {
         atomicAdd(&lcount[slot], 1);
@@ -1088,58 +847,6 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel_v4(
     }
     __syncthreads();
     for (int i = threadIdx.x; i < SLOTS; i += blockDim.x) {
-      KT key = lkeys[i];
-      if (key == EMPTY) continue;
-      int64_t gslot = gb_probe_insert((int64_t)key, tkeys, tsize);
-      atomicAdd((unsigned long long*)&gcount[gslot],
-                (unsigned long long)lcount[i]);
-      atomicAdd(&gaggs[gslot], laggs[i]);
-    }
-    __syncthreads();
-  }
-}
-
-// legacy (ILP-1) row loop kept for same-box A/B (FUGUE_GB_ILP=1)
-template <bool NT, typename KT>
-__global__ __launch_bounds__(BLOCK) void gb_aggregate_part_big_kernel_v1(
-    const KT* __restrict__ part_keys,
-    const double* __restrict__ part_vals,
-    const int32_t* __restrict__ ops,
-    int64_t n,
-    int64_t* __restrict__ tkeys,
-    double* __restrict__ gaggs,
-    int64_t* __restrict__ gcount,
-    int64_t tsize, int64_t chunk) {
-  __shared__ KT lkeys[LDS_SLOTS_BIG];
-  __shared__ double laggs[LDS_SLOTS_BIG];
-  __shared__ int lcount[LDS_SLOTS_BIG];
-  const KT EMPTY = lds_empty<KT>();
-  bool is_count = ops[0] == 3;
-  for (int64_t start = (int64_t)blockIdx.x * chunk; start < n;
-       start += (int64_t)gridDim.x * chunk) {
-    int64_t end = start + chunk;
-    if (end > n) end = n;
-    for (int i = threadIdx.x; i < LDS_SLOTS_BIG; i += blockDim.x) {
-      lkeys[i] = EMPTY;
-      lcount[i] = 0;
-      laggs[i] = 0.0;
-    }
-    __syncthreads();
-    for (int64_t i = start + threadIdx.x; i < end; i += blockDim.x) {
-      KT key = stream_ld<NT>(&part_keys[i]);
-      int slot = (int)(mix64((uint64_t)(int64_t)key) & (LDS_SLOTS_BIG - 1));
-      double v = is_count ? 1.0 : stream_ld<NT>(&part_vals[i]);
-      KT cur = lkeys[slot];
-      if (cur == key) {
-        atomicAdd(&lcount[slot], 1);
-        atomicAdd(&laggs[slot], v);
-      } else {
-        gb_lds_upsert<LDS_SLOTS_BIG, KT>(key, v, slot, EMPTY, lkeys, laggs, lcount, tkeys,
-                          gaggs, gcount, tsize);
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < LDS_SLOTS_BIG; i += blockDim.x) {
       KT key = lkeys[i];
       if (key == EMPTY) continue;
       int64_t gslot = gb_probe_insert((int64_t)key, tkeys, tsize);
@@ -1448,10 +1155,10 @@ void launch_expr_value(const void* prog, int64_t n, int out_int, void* out_v,
 }
 }  // extern "C"
 
-// P/E-variant dispatch for the v4 staged scatter: 512/8 (baseline),
-// 1024/4 and 2048/2 trade staging depth for finer partitions (smaller
-// phase-3 LDS tables -> higher phase-3 occupancy)
-template <bool NT, typename KT>
+// P/E-variant dispatch for the staged scatter: 512/8 (baseline), 1024/4
+// and 2048/2 trade staging depth for finer partitions (smaller phase-3
+// LDS tables -> higher phase-3 occupancy)
+template <typename KT>
 static void launch_scatter_v4_dispatch(int num_parts, dim3 g, dim3 b,
                                        hipStream_t stream,
                                        const int64_t* keys,
@@ -1461,26 +1168,25 @@ static void launch_scatter_v4_dispatch(int num_parts, dim3 g, dim3 b,
                                        int* ovf) {
   switch (num_parts) {
     case 1024:
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel_v4<NT, KT, 1024, 4>),
-                         g, b, 0, stream, keys, vals, n, shift, cursor, ok,
+      hipLaunchKernelGGL((gb_part_scatter_staged_kernel_v4<KT, 1024, 4>), g,
+                         b, 0, stream, keys, vals, n, shift, cursor, ok,
                          out_vals, chunk, ovf);
       break;
     case 2048:
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel_v4<NT, KT, 2048, 2>),
-                         g, b, 0, stream, keys, vals, n, shift, cursor, ok,
+      hipLaunchKernelGGL((gb_part_scatter_staged_kernel_v4<KT, 2048, 2>), g,
+                         b, 0, stream, keys, vals, n, shift, cursor, ok,
                          out_vals, chunk, ovf);
       break;
     default:
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel_v4<NT, KT, 512, 8>),
-                         g, b, 0, stream, keys, vals, n, shift, cursor, ok,
+      hipLaunchKernelGGL((gb_part_scatter_staged_kernel_v4<KT, 512, 8>), g,
+                         b, 0, stream, keys, vals, n, shift, cursor, ok,
                          out_vals, chunk, ovf);
   }
 }
 
-
-// SLOTS-variant dispatch for the v4 aggregate: 4096 (64KB LDS, 2
+// SLOTS-variant dispatch for the staged aggregate: 4096 (64KB LDS, 2
 // blocks/CU), 2048 (32KB, 5 blocks/CU), 1024 (16KB, 8 blocks/CU)
-template <bool NT, typename KT>
+template <typename KT>
 static void launch_agg_v4_dispatch(int slots, dim3 g, dim3 b,
                                    hipStream_t stream, const KT* pk,
                                    const double* part_vals,
@@ -1490,97 +1196,44 @@ static void launch_agg_v4_dispatch(int slots, dim3 g, dim3 b,
                                    int64_t chunk) {
   switch (slots) {
     case 1024:
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v4<NT, KT, 1024>), g,
-                         b, 0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
+      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v4<KT, 1024>), g, b, 0,
+                         stream, pk, part_vals, ops, n, tkeys, gaggs, gcount,
+                         tsize, chunk);
       break;
     case 2048:
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v4<NT, KT, 2048>), g,
-                         b, 0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
+      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v4<KT, 2048>), g, b, 0,
+                         stream, pk, part_vals, ops, n, tkeys, gaggs, gcount,
+                         tsize, chunk);
       break;
     default:
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v4<NT, KT, 4096>), g,
-                         b, 0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
+      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v4<KT, 4096>), g, b, 0,
+                         stream, pk, part_vals, ops, n, tkeys, gaggs, gcount,
+                         tsize, chunk);
   }
 }
-
 
 extern "C" {
-
-// Strict ILP env parsing: exact "1"/"2"/"4" only; anything else (typos,
-// "40", empty) warns once and selects the default depth.
-static int parse_ilp_env(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  if (v == nullptr) return dflt;
-  if (std::strcmp(v, "1") == 0) return 1;
-  if (std::strcmp(v, "2") == 0) return 2;
-  if (std::strcmp(v, "4") == 0) return 4;
-  static bool warned = false;
-  if (!warned) {
-    std::fprintf(stderr,
-                 "fugue_amd: unrecognized %s='%s' (expected 1/2/4); using "
-                 "default %d\n",
-                 name, v, dflt);
-    warned = true;
-  }
-  return dflt;
-}
 
 void launch_gb_part_scatter_staged(const int64_t* keys, const double* vals,
                                    int64_t n, int shift, int64_t* cursor,
                                    void* out_keys, double* out_vals,
-                                   int64_t chunk, int nt, int narrow,
-                                   int* ovf, int num_parts,
-                                   hipStream_t stream) {
+                                   int64_t chunk, int narrow, int* ovf,
+                                   int num_parts, hipStream_t stream) {
   if (chunk <= 0) chunk = SCATTER_CHUNK;
   int64_t blocks = (n + chunk - 1) / chunk;
   if (blocks > MAX_GRID) blocks = MAX_GRID;
   if (blocks < 1) blocks = 1;
   dim3 g((int)blocks), b(BLOCK);
-  // ILP depth of the scatter row loop: 4 (default, measured 5.06 vs
-  // 5.43 ms/step on the 125M-row bench), 2 = paired (512 parts only)
-  bool squad = parse_ilp_env("FUGUE_SC_ILP", 4) == 4 || num_parts != 512;
-  if (narrow) {
-    auto* ok = (int32_t*)out_keys;
-    if (squad && nt)
-      launch_scatter_v4_dispatch<true, int32_t>(num_parts, g, b, stream,
-                                                keys, vals, n, shift, cursor,
-                                                ok, out_vals, chunk, ovf);
-    else if (squad)
-      launch_scatter_v4_dispatch<false, int32_t>(num_parts, g, b, stream,
-                                                 keys, vals, n, shift,
-                                                 cursor, ok, out_vals, chunk,
-                                                 ovf);
-    else if (nt)
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel<true, int32_t>), g, b,
-                         0, stream, keys, vals, n, shift, cursor, ok,
-                         out_vals, chunk, ovf);
-    else
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel<false, int32_t>), g,
-                         b, 0, stream, keys, vals, n, shift, cursor, ok,
-                         out_vals, chunk, ovf);
-  } else {
-    auto* ok = (int64_t*)out_keys;
-    if (squad && nt)
-      launch_scatter_v4_dispatch<true, int64_t>(num_parts, g, b, stream,
-                                                keys, vals, n, shift, cursor,
-                                                ok, out_vals, chunk, nullptr);
-    else if (squad)
-      launch_scatter_v4_dispatch<false, int64_t>(num_parts, g, b, stream,
-                                                 keys, vals, n, shift,
-                                                 cursor, ok, out_vals, chunk,
-                                                 nullptr);
-    else if (nt)
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel<true, int64_t>), g, b,
-                         0, stream, keys, vals, n, shift, cursor, ok,
-                         out_vals, chunk, nullptr);
-    else
-      hipLaunchKernelGGL((gb_part_scatter_staged_kernel<false, int64_t>), g,
-                         b, 0, stream, keys, vals, n, shift, cursor, ok,
-                         out_vals, chunk, nullptr);
-  }
+  // ovf (speculative narrow: a key fell outside [0, 2^31)) only means
+  // something for int32 spill keys
+  if (narrow)
+    launch_scatter_v4_dispatch<int32_t>(num_parts, g, b, stream, keys, vals,
+                                        n, shift, cursor, (int32_t*)out_keys,
+                                        out_vals, chunk, ovf);
+  else
+    launch_scatter_v4_dispatch<int64_t>(num_parts, g, b, stream, keys, vals,
+                                        n, shift, cursor, (int64_t*)out_keys,
+                                        out_vals, chunk, nullptr);
 }
 
 void launch_gb_aggregate_part_big(const void* part_keys,
@@ -1588,8 +1241,8 @@ void launch_gb_aggregate_part_big(const void* part_keys,
                                   const int32_t* ops, int64_t n,
                                   int64_t* tkeys, double* gaggs,
                                   int64_t* gcount, int64_t tsize,
-                                  int64_t chunk, int nt, int narrow,
-                                  int slots, hipStream_t stream) {
+                                  int64_t chunk, int narrow, int slots,
+                                  hipStream_t stream) {
   // default chunk sweep-tuned per table size: 32K rows at 4096 slots
   // (2 blocks/CU), 16K at 2048 slots (5 blocks/CU; measured 4.03 vs
   // 4.42 ms on the 125M-row bench shape)
@@ -1598,68 +1251,20 @@ void launch_gb_aggregate_part_big(const void* part_keys,
   if (blocks > MAX_GRID) blocks = MAX_GRID;
   if (blocks < 1) blocks = 1;
   dim3 g((int)blocks), b(BLOCK);
-  // ILP depth of the row loop: 4 (default, measured 5.55 vs 5.63
-  // ms/step on the 125M-row bench), 2 = paired, 1 = legacy scalar
-  int ilp_d = parse_ilp_env("FUGUE_GB_ILP", 4);
-  bool legacy = ilp_d == 1;
-  bool quad = ilp_d == 4;
-  if (slots != 4096) legacy = false, quad = true;  // variants are v4-only
-  if (narrow) {
-    auto* pk = (const int32_t*)part_keys;
-    if (quad && nt)
-      launch_agg_v4_dispatch<true, int32_t>(slots, g, b, stream, pk,
-                                            part_vals, ops, n, tkeys, gaggs,
-                                            gcount, tsize, chunk);
-    else if (quad)
-      launch_agg_v4_dispatch<false, int32_t>(slots, g, b, stream, pk,
-                                             part_vals, ops, n, tkeys, gaggs,
-                                             gcount, tsize, chunk);
-    else if (legacy)
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v1<false, int32_t>), g,
-                         b, 0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
-    else if (nt)
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel<true, int32_t>), g, b,
-                         0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
-    else
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel<false, int32_t>), g, b,
-                         0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
-  } else {
-    auto* pk = (const int64_t*)part_keys;
-    if (quad && nt)
-      launch_agg_v4_dispatch<true, int64_t>(slots, g, b, stream, pk,
-                                            part_vals, ops, n, tkeys, gaggs,
-                                            gcount, tsize, chunk);
-    else if (quad)
-      launch_agg_v4_dispatch<false, int64_t>(slots, g, b, stream, pk,
-                                             part_vals, ops, n, tkeys, gaggs,
-                                             gcount, tsize, chunk);
-    else if (legacy)
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel_v1<false, int64_t>), g,
-                         b, 0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
-    else if (nt)
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel<true, int64_t>), g, b,
-                         0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
-    else
-      hipLaunchKernelGGL((gb_aggregate_part_big_kernel<false, int64_t>), g, b,
-                         0, stream, pk, part_vals, ops, n, tkeys, gaggs,
-                         gcount, tsize, chunk);
-  }
+  if (narrow)
+    launch_agg_v4_dispatch<int32_t>(slots, g, b, stream,
+                                    (const int32_t*)part_keys, part_vals, ops,
+                                    n, tkeys, gaggs, gcount, tsize, chunk);
+  else
+    launch_agg_v4_dispatch<int64_t>(slots, g, b, stream,
+                                    (const int64_t*)part_keys, part_vals, ops,
+                                    n, tkeys, gaggs, gcount, tsize, chunk);
 }
 
-}  // extern "C"
-
-extern "C" {
-
 void launch_gb_part_hist(const int64_t* keys, int64_t n, int shift,
-                         int64_t* hist, int num_parts, int64_t* minmax,
-                         hipStream_t stream) {
+                         int64_t* hist, int num_parts, hipStream_t stream) {
   hipLaunchKernelGGL(gb_part_hist_kernel, dim3(grid_for(n, 4)), dim3(BLOCK),
-                     0, stream, keys, n, shift, hist, num_parts, minmax);
+                     0, stream, keys, n, shift, hist, num_parts);
 }
 
 void launch_gb_part_scatter(const int64_t* keys, const double* vals,

@@ -10,6 +10,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import os
 import weakref
+from dataclasses import dataclass
 
 import numpy as np
 import pyarrow as pa
@@ -217,70 +218,13 @@ _KEY_STATS_MEMO_CAP = 128
 # (2 B + 4 B) = 10 B/row, plus keys and counts per GROUP; pkeys and pos
 # are dropped.  Two entries ~1.25GB each at 125M rows — bound the cache
 # tightly.
-_LAYOUT_MEMO: "Dict[Tuple[int, ...], Dict[str, Any]]" = {}
+_LAYOUT_MEMO: "Dict[Tuple[Any, ...], Any]" = {}
 _LAYOUT_MEMO_CAP = 2
 # key tensors seen once (candidates): recording uses the slower simple
 # scatter, so it only happens on the SECOND sight of the same keys —
 # one-shot group-bys never pay the record cost
-_LAYOUT_SEEN: "Dict[Tuple[int, ...], Any]" = {}
+_LAYOUT_SEEN: "Dict[Tuple[Any, ...], Any]" = {}
 _LAYOUT_SEEN_CAP = 16
-
-
-def _replay_tile() -> int:
-    """Rows per tile of the replay value scatter (FUGUE_GB_REPLAY_TILE):
-    a power of two in [512, 8192], or 0 to replay values by recorded
-    position (the pre-tile scatter, kept for A/B).  The layout is
-    recorded with a reservation chunk equal to the tile, so the rows of
-    one (tile, partition) leave as one contiguous run."""
-    tile = int(os.environ.get("FUGUE_GB_REPLAY_TILE", "8192"))
-    if tile == 0:
-        return 0
-    if tile < 512 or tile > 8192 or tile & (tile - 1):
-        raise ValueError(
-            f"FUGUE_GB_REPLAY_TILE={tile}: expected 0 or a power of two "
-            "in [512, 8192]"
-        )
-    return tile
-
-
-def _dense_slots() -> int:
-    """LDS table slots of the dense replay aggregate
-    (FUGUE_GB_DENSE_SLOTS: 2048, 4096 or 8192; 8 B per slot)."""
-    slots = int(os.environ.get("FUGUE_GB_DENSE_SLOTS", "4096"))
-    return slots if slots in (2048, 4096, 8192) else 4096
-
-
-def _prepare_dense_layout(
-    ext: Any, pkeys: "torch.Tensor", pos: "torch.Tensor", num_parts: int,
-    tile: int,
-) -> Optional[Dict[str, Any]]:
-    """One-time preparation of the dense replay layout from the recorded
-    partitioned keys (int64) and per-row spill positions; None when it is
-    declined (a partition's distinct keys overflow the id-assignment
-    table, or G >= 2^31) and the plain replay entry must be kept.  One
-    host readback, once per key tensor."""
-    offsets, distinct = ext.gb_dense_count(pkeys, num_parts)
-    group_base = torch.zeros(
-        num_parts + 1, dtype=torch.int64, device=pkeys.device
-    )
-    torch.cumsum(distinct, 0, out=group_base[1:])
-    dmax, n_groups = torch.stack([distinct.max(), group_base[-1]]).tolist()
-    if dmax > int(ext.dense_assign_max()) or n_groups >= (1 << 31):
-        return None
-    gid, out_keys, out_count = ext.gb_dense_assign(
-        pkeys, offsets, group_base, n_groups
-    )
-    ent: Dict[str, Any] = dict(
-        dense=True, dense_hits=0, gid=gid, offsets=offsets,
-        group_base=group_base, n_groups=int(n_groups), out_keys=out_keys,
-        out_count=out_count, tile=tile,
-    )
-    if tile > 0:
-        ent["rank"], ent["dst"] = ext.scatter_tile_prepare(pos, tile)
-    else:
-        ent["rank"], ent["dst"] = None, pos
-    return ent
-
 
 def _key_stats_device(
     datas: "List[torch.Tensor]",
@@ -348,6 +292,269 @@ def _layout_second_sight(lkey: tuple, packed: "torch.Tensor") -> bool:
         _LAYOUT_SEEN.pop(next(iter(_LAYOUT_SEEN)))
     _LAYOUT_SEEN[lkey] = weakref.ref(packed)
     return False
+
+
+@dataclass
+class _PlainLayout:
+    """Recorded layout replayed through ``gb_aggregate_replay``."""
+
+    ref: Any  # weakref to the packed key tensor the layout was made from
+    pkeys: "torch.Tensor"  # spill keys (int32 when the keys fit 31 bits)
+    pos: "torch.Tensor"  # spill position of every row
+
+
+@dataclass
+class _DenseLayout:
+    """Recorded layout replayed through ``gb_replay_dense``: the value
+    scatter is either tile-coalesced (``tile`` > 0: ``rank`` and ``dst``
+    from ``scatter_tile_prepare``) or by recorded position (``tile`` ==
+    0: ``pos``)."""
+
+    ref: Any
+    gid: "torch.Tensor"
+    offsets: "torch.Tensor"
+    group_base: "torch.Tensor"
+    n_groups: int
+    out_keys: "torch.Tensor"
+    out_count: "torch.Tensor"
+    rank: Optional["torch.Tensor"]
+    dst: Optional["torch.Tensor"]
+    pos: Optional["torch.Tensor"]
+    tile: int
+    hits: int = 0  # replayed steps served by this entry
+
+
+def _layout_get(lkey: tuple) -> Any:
+    """The memoized layout for this key while its key tensor is alive."""
+    ent = _LAYOUT_MEMO.get(lkey)
+    return ent if ent is not None and ent.ref() is not None else None
+
+
+def _layout_put(lkey: tuple, ent: Any) -> None:
+    if len(_LAYOUT_MEMO) >= _LAYOUT_MEMO_CAP:
+        _LAYOUT_MEMO.pop(next(iter(_LAYOUT_MEMO)))
+    _LAYOUT_MEMO[lkey] = ent
+
+
+def _prepare_dense_layout(
+    ext: Any, packed: "torch.Tensor", pkeys: "torch.Tensor",
+    pos: "torch.Tensor", num_parts: int, tile: int,
+) -> Optional[_DenseLayout]:
+    """One-time preparation of the dense replay layout from the recorded
+    partitioned keys (int64) and per-row spill positions; None when it is
+    declined (a partition's distinct keys overflow the id-assignment
+    table, or G >= 2^31) and the plain replay entry must be kept.  One
+    host readback, once per key tensor."""
+    offsets, distinct = ext.gb_dense_count(pkeys=pkeys, num_parts=num_parts)
+    group_base = torch.zeros(
+        num_parts + 1, dtype=torch.int64, device=pkeys.device
+    )
+    torch.cumsum(distinct, 0, out=group_base[1:])
+    dmax, n_groups = torch.stack([distinct.max(), group_base[-1]]).tolist()
+    if dmax > int(ext.dense_assign_max()) or n_groups >= (1 << 31):
+        return None
+    gid, out_keys, out_count = ext.gb_dense_assign(
+        pkeys=pkeys, offsets=offsets, group_base=group_base,
+        n_groups=n_groups,
+    )
+    rank = dst = None
+    if tile > 0:
+        rank, dst = ext.scatter_tile_prepare(pos, tile)
+    return _DenseLayout(
+        ref=weakref.ref(packed), gid=gid, offsets=offsets,
+        group_base=group_base, n_groups=int(n_groups), out_keys=out_keys,
+        out_count=out_count, rank=rank, dst=dst,
+        pos=None if tile > 0 else pos, tile=tile,
+    )
+
+
+@dataclass(frozen=True)
+class _GbKnobs:
+    """The FUGUE_GB_* tuning knobs of the partitioned group-by, read from
+    the environment once per ``groupby_aggregate`` call (A/B scripts and
+    tests change them between calls in one process)."""
+
+    staged_max: int = 1_200_000  # FUGUE_GB_STAGED_MAX
+    parts: int = 1024  # FUGUE_GB_PARTS: 512, 1024 or 2048
+    scatter_chunk: int = 0  # FUGUE_GB_SCATTER_CHUNK (0: kernel default)
+    agg_chunk: int = 0  # FUGUE_GB_AGG_CHUNK (0: kernel default)
+    narrow: bool = True  # FUGUE_GB_NARROW
+    staged_min_rows: int = 48_000_000  # FUGUE_GB_STAGED_MIN_ROWS
+    layout_reuse: bool = True  # FUGUE_GB_LAYOUT_REUSE
+    replay_dense: bool = True  # FUGUE_GB_REPLAY_DENSE
+    # FUGUE_GB_REPLAY_TILE: rows per tile of the replay value scatter, a
+    # power of two in [512, 8192], or 0 to replay values by recorded
+    # position (the pre-tile scatter, kept for A/B).  The layout is
+    # recorded with a reservation chunk equal to the tile, so the rows of
+    # one (tile, partition) leave as one contiguous run.
+    replay_tile: int = 8192
+    # FUGUE_GB_DENSE_SLOTS: LDS table slots of the dense replay
+    # aggregate (2048, 4096 or 8192; 8 B per slot)
+    dense_slots: int = 4096
+
+    @classmethod
+    def from_env(cls) -> "_GbKnobs":
+        env = os.environ.get
+        parts = int(env("FUGUE_GB_PARTS", "1024"))
+        tile = int(env("FUGUE_GB_REPLAY_TILE", "8192"))
+        if tile != 0 and (tile < 512 or tile > 8192 or tile & (tile - 1)):
+            raise ValueError(
+                f"FUGUE_GB_REPLAY_TILE={tile}: expected 0 or a power of two "
+                "in [512, 8192]"
+            )
+        slots = int(env("FUGUE_GB_DENSE_SLOTS", "4096"))
+        return cls(
+            staged_max=int(env("FUGUE_GB_STAGED_MAX", "1200000")),
+            parts=parts if parts in (512, 1024, 2048) else 512,
+            scatter_chunk=int(env("FUGUE_GB_SCATTER_CHUNK", "0")),
+            agg_chunk=int(env("FUGUE_GB_AGG_CHUNK", "0")),
+            narrow=bool(int(env("FUGUE_GB_NARROW", "1"))),
+            staged_min_rows=int(env("FUGUE_GB_STAGED_MIN_ROWS", "48000000")),
+            layout_reuse=env("FUGUE_GB_LAYOUT_REUSE", "1") != "0",
+            replay_dense=env("FUGUE_GB_REPLAY_DENSE", "1") != "0",
+            replay_tile=tile,
+            dense_slots=slots if slots in (2048, 4096, 8192) else 4096,
+        )
+
+
+@dataclass(frozen=True)
+class _GbPlan:
+    """How one high-cardinality group-by runs (``_plan_partitioned``)."""
+
+    num_parts: int
+    tsize: int  # global group table slots
+    narrow: int  # int32 spill keys: 1 yes, 0 no, -1 speculative
+    force_simple: bool  # simple scatter instead of the LDS-staged one
+    reuse: bool  # record / replay the partition layout
+    dense_ok: bool  # a recorded layout may be the dense kind
+    tile: int  # replay scatter tile (0: by position)
+    sc_chunk: int
+    ag_chunk: int
+
+
+def _table_size(expected_groups: int) -> int:
+    return _next_pow2(max(16, int(expected_groups * 2)))
+
+
+def _plan_partitioned(
+    n: int,
+    expected_groups: int,
+    n_aggs: int,
+    fp64_sum: bool,
+    key_bits: Optional[int],
+    key_range: Optional[Tuple[int, int]],
+    knobs: _GbKnobs,
+) -> _GbPlan:
+    """Plan the 2-phase partitioned aggregation (hash-partition rows so
+    each partition's groups fit the per-workgroup LDS table) of ``n``
+    rows with ``n_aggs`` SUM/COUNT aggregates over null-free inputs.
+    ``fp64_sum``: the single aggregate is a SUM of an fp64 column.
+    ``key_bits``: packed key width when the keys were packed (pack meta);
+    ``key_range``: measured (lo, hi) of unpacked keys when known."""
+    # single-agg path with moderate cardinality uses the LDS
+    # write-staged scatter (512 parts, 4096-slot phase-3 table)
+    if n_aggs <= 1 and expected_groups <= knobs.staged_max:
+        # staged-variant partition count: 512 (8-deep staging,
+        # 4096-slot phase-3), 1024 (4-deep, 2048-slot) or 2048
+        # (2-deep, 1024-slot) — smaller tables run phase 3 at
+        # higher occupancy; A/B via FUGUE_GB_PARTS
+        num_parts = knobs.parts
+    else:
+        num_parts = min(4096, _next_pow2(max(16, expected_groups // 512)))
+    # int32 intermediate keys shrink the partitioned spill 16B->12B
+    # per row (and its MALL footprint) when the packed key range is
+    # known (pack meta) or measured to fit 31 bits
+    narrow = 0
+    if knobs.narrow:
+        if key_bits is not None:
+            narrow = 1 if key_bits <= 31 else 0
+        elif key_range is not None:
+            narrow = 1 if key_range[0] >= 0 and key_range[1] < (1 << 31) else 0
+        else:
+            narrow = -1  # speculative: overflow flag checked after the run
+    # the LDS write-staged scatter pays off only on big spills; at
+    # q3-like sizes the simple per-chunk-reservation variant is
+    # faster (same-box A/B, profiles/NOTES.md r02)
+    force_simple = n < knobs.staged_min_rows
+    reuse = (
+        knobs.layout_reuse
+        and n_aggs == 1
+        and n < (1 << 31)
+        and num_parts in (512, 1024, 2048)
+    )
+    # dense replay (FUGUE_GB_REPLAY_DENSE, default on): the zero-copy
+    # condition of the aggregate input plus the op
+    dense_ok = reuse and knobs.replay_dense and n_aggs == 1 and fp64_sum
+    return _GbPlan(
+        num_parts=num_parts,
+        tsize=_table_size(expected_groups),
+        narrow=narrow,
+        force_simple=force_simple,
+        reuse=reuse,
+        dense_ok=dense_ok,
+        tile=knobs.replay_tile if dense_ok else 0,
+        sc_chunk=knobs.scatter_chunk,
+        ag_chunk=knobs.agg_chunk,
+    )
+
+
+def _run_partitioned(
+    ext: Any, packed: "torch.Tensor", vals: "torch.Tensor",
+    ops: "torch.Tensor", plan: _GbPlan, *, record: bool = False,
+) -> Tuple["torch.Tensor", ...]:
+    """Run the planned aggregation: (tkeys, gaggs, gcount, pkeys, pos).
+    ``record`` keeps the wide spill keys and every row's spill position
+    (simple scatter, reservation chunk = replay tile) for a layout entry;
+    otherwise pkeys/pos are scratch."""
+
+    def run(narrow: int) -> List["torch.Tensor"]:
+        return ext.gb_aggregate_partitioned(
+            keys=packed, vals=vals, ops=ops, num_parts=plan.num_parts,
+            tsize=plan.tsize, scatter_chunk=plan.sc_chunk,
+            agg_chunk=plan.ag_chunk, narrow=narrow, record_layout=record,
+            force_simple=plan.force_simple and not record,
+            record_chunk=plan.tile if record else 0,
+        )
+
+    tkeys, gaggs, gcount, ovf, pkeys, pos = run(0 if record else plan.narrow)
+    if not record and plan.narrow == -1 and int(ovf.item()) != 0:
+        # a key fell outside [0, 2^31): redo exactly, wide keys
+        tkeys, gaggs, gcount, ovf, pkeys, pos = run(0)
+    return tkeys, gaggs, gcount, pkeys, pos
+
+
+def _compact_groups(
+    ext: Any, tkeys: "torch.Tensor", gcount: "torch.Tensor",
+    gaggs: "torch.Tensor", aggs: List[Tuple[str, int, str]],
+    extra: Optional["torch.Tensor"] = None,
+) -> Tuple["torch.Tensor", Dict[str, "torch.Tensor"], "torch.Tensor", Any]:
+    """Occupied slots of a group table as (keys, {out_name: values},
+    counts, extra) in table order; ``extra`` is an optional per-slot
+    int64 column compacted alongside.  Deterministic own-kernel
+    compaction (replaces nonzero + per-column index_select); ONE host
+    read for the total."""
+    if len(aggs) > 6:  # beyond the kernel's by-value pointer pack
+        occupied = (tkeys != GB_EMPTY).nonzero(as_tuple=True)[0]
+        return (
+            tkeys.index_select(0, occupied),
+            {
+                oname: gaggs[i].index_select(0, occupied)
+                for i, (_, _, oname) in enumerate(aggs)
+            },
+            gcount.index_select(0, occupied),
+            None if extra is None else extra.index_select(0, occupied),
+        )
+    ck, cc, ca, ce, bases = ext.gb_compact(tkeys, gcount, gaggs, extra)
+    total = int(bases[-1].item())
+    return (
+        ck.narrow(0, 0, total),
+        {
+            oname: ca[i].narrow(0, 0, total)
+            for i, (_, _, oname) in enumerate(aggs)
+        },
+        cc.narrow(0, 0, total),
+        None if extra is None else ce.narrow(0, 0, total),
+    )
 
 
 def _device_packable(key_cols: "Sequence[DeviceColumn]") -> bool:
@@ -529,6 +736,39 @@ def _agg_input(c, n: int) -> "torch.Tensor":
     return c.data.to(torch.float64)
 
 
+def _agg_inputs(
+    df: HipDataFrame, aggs: List[Tuple[str, int, str]], n: int, device: Any
+) -> Tuple["torch.Tensor", Optional["torch.Tensor"], "torch.Tensor", bool]:
+    """Kernel inputs for ``aggs``: (vals [A, n] fp64, valids [A, n] or
+    None, ops [A] int32, zero_copy).  ``zero_copy``: the single aggregate
+    reads a null-free fp64 column in place.  No aggregates at all run as
+    one COUNT."""
+    if len(aggs) == 0:
+        return (
+            torch.zeros((1, n), dtype=torch.float64, device=device),
+            None,
+            torch.tensor([AGG_COUNT], dtype=torch.int32, device=device),
+            False,
+        )
+    ops = torch.tensor(
+        [op for _, op, _ in aggs], dtype=torch.int32, device=device
+    )
+    if len(aggs) == 1:
+        c = df.col(aggs[0][0])
+        if c.data.dtype == torch.float64 and c.valid is None:
+            return c.data.unsqueeze(0), None, ops, True
+    vals = torch.empty((len(aggs), n), dtype=torch.float64, device=device)
+    valids: Optional[torch.Tensor] = None
+    if any(df.col(c).valid is not None for c, _, _ in aggs):
+        valids = torch.ones((len(aggs), n), dtype=torch.bool, device=device)
+    for i, (cname, _, _) in enumerate(aggs):
+        c = df.col(cname)
+        vals[i] = _agg_input(c, n)
+        if valids is not None and c.valid is not None:
+            valids[i] = c.valid
+    return vals, valids, ops, False
+
+
 def groupby_aggregate(
     df: HipDataFrame,
     keys: List[str],
@@ -547,41 +787,11 @@ def groupby_aggregate(
     device = df.col(keys[0]).data.device if keys else torch.device(df.device)
     key_cols = [df.col(k) for k in keys]
     packed, meta = pack_keys(key_cols, mins=pack_mins, widths=pack_widths)
-    n_aggs = len(aggs)
-    if (
-        n_aggs == 1
-        and df.col(aggs[0][0]).data.dtype == torch.float64
-        and df.col(aggs[0][0]).valid is None
-    ):
-        # zero-copy: single fp64 agg column used in place
-        vals = df.col(aggs[0][0]).data.unsqueeze(0)
-        valids = None
-        ops = torch.tensor(
-            [aggs[0][1]], dtype=torch.int32, device=device
-        )
-    elif n_aggs > 0:
-        vals = torch.empty((n_aggs, n), dtype=torch.float64, device=device)
-        any_null = any(df.col(c).valid is not None for c, _, _ in aggs)
-        valids: Optional[torch.Tensor] = None
-        if any_null:
-            valids = torch.ones((n_aggs, n), dtype=torch.bool, device=device)
-        for i, (cname, op, _) in enumerate(aggs):
-            c = df.col(cname)
-            vals[i] = _agg_input(c, n)
-            if valids is not None and c.valid is not None:
-                valids[i] = c.valid
-        ops = torch.tensor(
-            [op for _, op, _ in aggs], dtype=torch.int32, device=device
-        )
-    else:
-        vals = torch.zeros((1, n), dtype=torch.float64, device=device)
-        valids = None
-        ops = torch.tensor([AGG_COUNT], dtype=torch.int32, device=device)
-        n_aggs = 0
+    vals, valids, ops, zero_copy = _agg_inputs(df, aggs, n, device)
     if _is_cpu(packed):
         return _groupby_aggregate_cpu(packed, aggs, df, meta)
     ext = get_ext()
-    key_lo = key_hi = None
+    key_range = None
     if expected_groups is None:
         # sample-based distinct-count estimate (Chao83: D ≈ d + f1²/(2·f2),
         # robust when the sample is mostly singletons — a linear scale-up
@@ -590,10 +800,10 @@ def groupby_aggregate(
         # carries min/max so the int32-narrowing decision needs no
         # speculative overflow check.
         if meta is None and n > 0:
-            key_lo_l, key_hi_l, expected_groups = _key_stats_device(
+            key_lo, key_hi, expected_groups = _key_stats_device(
                 [packed], [None], True
             )
-            key_lo, key_hi = key_lo_l[0], key_hi_l[0]
+            key_range = (key_lo[0], key_hi[0])
         elif n > 0:
             expected_groups = (meta or {}).get("est")
             if expected_groups is None:
@@ -602,75 +812,30 @@ def groupby_aggregate(
                 )
         else:
             expected_groups = 1
-    tsize = _next_pow2(max(16, int(expected_groups * 2)))
     sum_count_only = all(op in (AGG_SUM, AGG_COUNT) for _, op, _ in aggs)
-    if expected_groups > 100_000 and valids is None and sum_count_only:
-        # high cardinality: 2-phase partitioned aggregation (hash-partition
-        # rows so each partition's groups fit the per-workgroup LDS table)
-        # single-agg path with moderate cardinality uses the LDS
-        # write-staged scatter (512 parts, 4096-slot phase-3 table)
-        staged_max = int(os.environ.get("FUGUE_GB_STAGED_MAX", "1200000"))
-        if len(aggs) <= 1 and expected_groups <= staged_max:
-            # staged-variant partition count: 512 (8-deep staging,
-            # 4096-slot phase-3), 1024 (4-deep, 2048-slot) or 2048
-            # (2-deep, 1024-slot) — smaller tables run phase 3 at
-            # higher occupancy; A/B via FUGUE_GB_PARTS
-            num_parts = int(os.environ.get("FUGUE_GB_PARTS", "1024"))
-            if num_parts not in (512, 1024, 2048):
-                num_parts = 512
-        else:
-            num_parts = min(4096, _next_pow2(max(16, expected_groups // 512)))
-        sc_chunk = int(os.environ.get("FUGUE_GB_SCATTER_CHUNK", "0"))
-        ag_chunk = int(os.environ.get("FUGUE_GB_AGG_CHUNK", "0"))
-        nt = int(os.environ.get("FUGUE_GB_NT", "0"))
-        # int32 intermediate keys shrink the partitioned spill 16B->12B
-        # per row (and its MALL footprint) when the packed key range is
-        # known (pack meta) or measured to fit 31 bits
-        narrow = 0
-        if int(os.environ.get("FUGUE_GB_NARROW", "1")):
-            if meta is not None:
-                narrow = 1 if sum(meta["widths"]) <= 31 else 0
-            elif key_lo is not None:
-                narrow = 1 if key_lo >= 0 and key_hi < (1 << 31) else 0
-            else:
-                narrow = -1  # speculative: overflow flag checked below
-        slots = {512: 4096, 1024: 2048, 2048: 1024}.get(num_parts, 4096)
-        # the LDS write-staged scatter pays off only on big spills; at
-        # q3-like sizes the simple per-chunk-reservation variant is
-        # faster (same-box A/B, profiles/NOTES.md r02)
-        force_simple = n < int(
-            os.environ.get("FUGUE_GB_STAGED_MIN_ROWS", "48000000")
+    if not (expected_groups > 100_000 and valids is None and sum_count_only):
+        use_lds = expected_groups <= 100_000 and sum_count_only
+        tkeys, gaggs, gcount = ext.gb_aggregate(
+            keys=packed, vals=vals, valids=valids, ops=ops,
+            tsize=_table_size(expected_groups), use_lds=use_lds,
         )
-        reuse = (
-            os.environ.get("FUGUE_GB_LAYOUT_REUSE", "1") != "0"
-            and len(aggs) == 1
-            and n < (1 << 31)
-            and num_parts in (512, 1024, 2048)
+    else:
+        # high cardinality: 2-phase partitioned aggregation
+        knobs = _GbKnobs.from_env()
+        plan = _plan_partitioned(
+            n, expected_groups, len(aggs),
+            zero_copy and aggs[0][1] == AGG_SUM,
+            None if meta is None else sum(meta["widths"]),
+            key_range, knobs,
         )
-        # dense replay (FUGUE_GB_REPLAY_DENSE, default on): the zero-copy
-        # condition above plus the op.  The gate and the
-        # scatter tile are part of the memo key so an in-process A/B keeps
-        # one entry per side.
-        dense_ok = (
-            reuse
-            and os.environ.get("FUGUE_GB_REPLAY_DENSE", "1") != "0"
-            and valids is None
-            and n_aggs == 1
-            and aggs[0][1] == AGG_SUM
-            and vals.dim() == 2
-            and vals.size(0) == 1
-            and df.col(aggs[0][0]).data.dtype == torch.float64
-        )
-        tile = _replay_tile() if dense_ok else 0
+        # the dense gate and the scatter tile are part of the memo key so
+        # an in-process A/B keeps one entry per side
         lkey = (
-            packed.data_ptr(), n, num_parts, tsize, narrow, dense_ok, tile,
+            packed.data_ptr(), n, plan.num_parts, plan.tsize, plan.narrow,
+            plan.dense_ok, plan.tile,
         )
-        ent = _LAYOUT_MEMO.get(lkey) if reuse else None
-        if (
-            ent is not None
-            and ent["ref"]() is not None
-            and ent.get("dense")
-        ):
+        ent = _layout_get(lkey) if plan.reuse else None
+        if isinstance(ent, _DenseLayout):
             # dense replay: groups, counts, output order and every row's
             # group were fixed when the layout was recorded; the step is
             # the value scatter + one LDS add per row.  The SAME cached
@@ -679,100 +844,46 @@ def groupby_aggregate(
             # lets the identity-memoized key stats of a downstream join
             # hit instead of re-running.
             out_sum = ext.gb_replay_dense(
-                vals, ent["rank"], ent["dst"], ent["gid"], ent["offsets"],
-                ent["group_base"], ent["n_groups"], ent["tile"], ag_chunk,
-                _dense_slots(),
+                vals=vals, gid=ent.gid, offsets=ent.offsets,
+                group_base=ent.group_base, n_groups=ent.n_groups,
+                chunk=plan.ag_chunk, slots=knobs.dense_slots,
+                tile=ent.tile, rank=ent.rank, dst=ent.dst, pos=ent.pos,
             )
-            ent["dense_hits"] += 1
-            return (
-                ent["out_keys"], {aggs[0][2]: out_sum}, ent["out_count"],
-                meta,
-            )
-        if ent is not None and ent["ref"]() is not None:
+            ent.hits += 1
+            return ent.out_keys, {aggs[0][2]: out_sum}, ent.out_count, meta
+        if ent is not None:
             # replay: fresh values through the recorded layout — phase 1
             # (hist) and the key scatter are skipped entirely
             tkeys, gaggs, gcount = ext.gb_aggregate_replay(
-                ent["pkeys"], ent["pos"], vals, ops, tsize, ag_chunk, nt,
-                slots,
+                pkeys=ent.pkeys, pos=ent.pos, vals=vals, ops=ops,
+                num_parts=plan.num_parts, tsize=plan.tsize,
+                agg_chunk=plan.ag_chunk,
             )
-        elif reuse and not _layout_second_sight(lkey, packed):
-            # first sight of these keys: normal path (recording uses the
-            # slower simple scatter; only repeat keys justify it)
-            tkeys, gaggs, gcount, ovf, _pk, _pos = (
-                ext.gb_aggregate_partitioned(
-                    packed, vals, ops, num_parts, tsize, sc_chunk,
-                    ag_chunk, nt, narrow, False, force_simple
-                )
-            )
-            if narrow == -1 and int(ovf.item()) != 0:
-                tkeys, gaggs, gcount, ovf, _pk, _pos = (
-                    ext.gb_aggregate_partitioned(
-                        packed, vals, ops, num_parts, tsize, sc_chunk,
-                        ag_chunk, nt, 0, False, force_simple
-                    )
-                )
-        elif reuse:
-            tkeys, gaggs, gcount, ovf, pkeys_l, pos = (
-                ext.gb_aggregate_partitioned(
-                    packed, vals, ops, num_parts, tsize, sc_chunk,
-                    ag_chunk, nt, 0, True, False, tile
-                )
+        elif plan.reuse and _layout_second_sight(lkey, packed):
+            # second sight of these keys: record the layout (recording
+            # uses the slower simple scatter; only repeat keys justify it)
+            tkeys, gaggs, gcount, pkeys, pos = _run_partitioned(
+                ext, packed, vals, ops, plan, record=True
             )
             new_ent = None
-            if dense_ok:
+            if plan.dense_ok:
                 new_ent = _prepare_dense_layout(
-                    ext, pkeys_l, pos, num_parts, tile
+                    ext, packed, pkeys, pos, plan.num_parts, plan.tile
                 )
             if new_ent is None:
-                if narrow == 1:
-                    pkeys_l = pkeys_l.to(torch.int32)
-                new_ent = dict(pkeys=pkeys_l, pos=pos, dense=False)
-            new_ent["ref"] = weakref.ref(packed)
-            if len(_LAYOUT_MEMO) >= _LAYOUT_MEMO_CAP:
-                _LAYOUT_MEMO.pop(next(iter(_LAYOUT_MEMO)))
-            _LAYOUT_MEMO[lkey] = new_ent
+                if plan.narrow == 1:
+                    pkeys = pkeys.to(torch.int32)
+                new_ent = _PlainLayout(weakref.ref(packed), pkeys, pos)
+            _layout_put(lkey, new_ent)
         else:
-            tkeys, gaggs, gcount, ovf, _pk, _pos = (
-                ext.gb_aggregate_partitioned(
-                    packed, vals, ops, num_parts, tsize, sc_chunk,
-                    ag_chunk, nt, narrow, False, force_simple
-                )
+            tkeys, gaggs, gcount, _, _ = _run_partitioned(
+                ext, packed, vals, ops, plan
             )
-            if narrow == -1 and int(ovf.item()) != 0:
-                # a key fell outside [0, 2^31): redo exactly, wide keys
-                tkeys, gaggs, gcount, ovf, _pk, _pos = (
-                    ext.gb_aggregate_partitioned(
-                        packed, vals, ops, num_parts, tsize, sc_chunk,
-                        ag_chunk, nt, 0, False, force_simple
-                    )
-                )
-    else:
-        use_lds = expected_groups <= 100_000 and sum_count_only
-        tkeys, gaggs, gcount = ext.gb_aggregate(
-            packed, vals, valids, ops, tsize, use_lds
-        )
-    # deterministic own-kernel compaction of the group table (replaces
-    # nonzero + per-column index_select); ONE host read for the total
-    if len(aggs) > 6:  # beyond the kernel's by-value pointer pack
-        occupied = (tkeys != GB_EMPTY).nonzero(as_tuple=True)[0]
-        out_keys = tkeys.index_select(0, occupied)
-        out_count = gcount.index_select(0, occupied)
-        out_aggs: Dict[str, torch.Tensor] = {}
-        for i, (_, op, oname) in enumerate(aggs):
-            out_aggs[oname] = gaggs[i].index_select(0, occupied)
-        return out_keys, out_aggs, out_count, meta
-    ck, cc, ca, _ce, bases = ext.gb_compact(
-        tkeys, gcount,
-        gaggs if len(aggs) > 0
-        else torch.empty((0, 0), dtype=torch.float64, device=device),
-        None,
+    if len(aggs) == 0:
+        gaggs = torch.empty((0, 0), dtype=torch.float64, device=device)
+    out_keys, out_aggs, out_count, _ = _compact_groups(
+        ext, tkeys, gcount, gaggs, aggs
     )
-    total = int(bases[-1].item())
-    out_keys = ck.narrow(0, 0, total)
-    out_count = cc.narrow(0, 0, total)
-    out_aggs = {}
-    for i, (_, op, oname) in enumerate(aggs):
-        out_aggs[oname] = ca[i].narrow(0, 0, total)
     return out_keys, out_aggs, out_count, meta
 
 
@@ -1009,21 +1120,9 @@ def groupby_aggregate_hashed(
     rep, th2, conflict = ext.gb_mark_reps(h1, h2, tkeys, tsize)
     if int(conflict.item()) > 0:
         raise HashCollisionError("h1 collision on string keys")
-    if len(aggs) > 6:  # beyond the kernel's by-value pointer pack
-        occupied = (tkeys != GB_EMPTY).nonzero(as_tuple=True)[0]
-        reps = rep.index_select(0, occupied)
-        counts = gcount.index_select(0, occupied)
-        out_aggs: Dict[str, torch.Tensor] = {}
-        for i, (_, op, oname) in enumerate(aggs):
-            out_aggs[oname] = gaggs[i].index_select(0, occupied)
-        return reps, out_aggs, counts
-    ck, cc, ca, ce, bases = ext.gb_compact(tkeys, gcount, gaggs, rep)
-    total = int(bases[-1].item())
-    reps = ce.narrow(0, 0, total)
-    counts = cc.narrow(0, 0, total)
-    out_aggs = {}
-    for i, (_, op, oname) in enumerate(aggs):
-        out_aggs[oname] = ca[i].narrow(0, 0, total)
+    _, out_aggs, counts, reps = _compact_groups(
+        ext, tkeys, gcount, gaggs, aggs, extra=rep
+    )
     return reps, out_aggs, counts
 
 

@@ -42,7 +42,7 @@ def _entry(keys):
     ents = [
         e for k, e in dops._LAYOUT_MEMO.items()
         if k[0] == keys.data_ptr() and k[1] == keys.numel()
-        and e["ref"]() is not None
+        and e.ref() is not None
     ]
     assert len(ents) == 1, "expected exactly one layout entry for the keys"
     return ents[0]
@@ -74,8 +74,8 @@ def _run_case(keys, expected_groups, seed, expect_dense):
         ), call
         if call >= 2:
             ent = _entry(keys)
-            assert bool(ent["dense"]) == expect_dense
-            hits = ent.get("dense_hits", 0)
+            assert isinstance(ent, dops._DenseLayout) == expect_dense
+            hits = ent.hits if expect_dense else 0
             assert hits == (max(0, call - 2) if expect_dense else 0), call
     return ent
 
@@ -84,7 +84,8 @@ def test_dense_replay_base_shape():
     keys = torch.randint(0, 200_000, (300_001,), dtype=torch.int64,
                          device="cuda", generator=_gen(11))
     ent = _run_case(keys, 200_000, 12, True)
-    assert "pkeys" not in ent  # dense entries drop the cached spill keys
+    # dense entries drop the cached spill keys
+    assert not hasattr(ent, "pkeys")
 
 
 def test_dense_replay_sparse():
@@ -134,7 +135,7 @@ def test_dense_replay_declined():
     perm = torch.randperm(n, device="cuda", generator=_gen(51))
     keys = (perm % 3_000_000).to(torch.int64)
     ent = _run_case(keys, 1_100_000, 52, False)
-    assert ent["dense"] is False and "pkeys" in ent
+    assert isinstance(ent, dops._PlainLayout) and ent.pkeys is not None
 
 
 def test_dense_replay_new_key_tensor():
@@ -148,8 +149,8 @@ def test_dense_replay_new_key_tensor():
     out_keys, out_aggs, out_count, _ = _agg(
         DeviceColumn(keys2, None, pa.int64()), vals, 200_000
     )
-    assert ent["dense_hits"] == 2  # the old layout was not replayed
-    assert out_keys is not ent["out_keys"]
+    assert ent.hits == 2  # the old layout was not replayed
+    assert out_keys is not ent.out_keys
     uniq, inv = torch.unique(keys2, return_inverse=True)
     ref = torch.zeros(uniq.numel(), dtype=torch.float64, device="cuda")
     ref.scatter_add_(0, inv, vals)
@@ -166,7 +167,8 @@ def test_dense_replay_gate_off(monkeypatch):
     keys = torch.randint(0, 200_000, (300_001,), dtype=torch.int64,
                          device="cuda", generator=_gen(71))
     ent = _run_case(keys, 200_000, 72, False)
-    assert "pkeys" in ent and "gid" not in ent
+    assert isinstance(ent, dops._PlainLayout) and ent.pkeys is not None
+    assert not hasattr(ent, "gid")
 
 
 @pytest.mark.parametrize("tile", [512, 8192])
