@@ -1,5 +1,5 @@
-// Torch-extension bindings for the CDNA4 relational kernels
-// (fugue_amd/hip/csrc/relational.hip).
+// Torch-extension bindings for the CDNA4 relational kernels (the .hip
+// files beside this one; launchers and shared limits in relational.h).
 #include <torch/extension.h>
 
 #include <c10/hip/HIPStream.h>
@@ -11,122 +11,7 @@
 #include <limits>
 #include <vector>
 
-extern "C" {
-void launch_hash_col_i64(const int64_t*, const bool*, uint64_t*, int64_t, int,
-                         hipStream_t);
-void launch_hash_col_i32(const int32_t*, const bool*, uint64_t*, int64_t, int,
-                         hipStream_t);
-void launch_hash_col_f64(const double*, const bool*, uint64_t*, int64_t, int,
-                         hipStream_t);
-void launch_hash_col_f32(const float*, const bool*, uint64_t*, int64_t, int,
-                         hipStream_t);
-void launch_hash_col_i8(const int8_t*, const bool*, uint64_t*, int64_t, int,
-                        hipStream_t);
-void launch_bucket_of(const uint64_t*, int32_t*, int64_t, int32_t,
-                      hipStream_t);
-void launch_histogram(const int32_t*, int64_t*, int64_t, int32_t, hipStream_t);
-void launch_scatter(const int32_t*, int64_t*, int64_t*, int64_t, hipStream_t);
-void launch_gb_aggregate(const int64_t*, const double*, const bool*,
-                         const int32_t*, int, int64_t, int64_t*, double*,
-                         int64_t*, int64_t, int, hipStream_t);
-void launch_join_emit_unique(const int64_t*, int64_t, const int64_t*,
-                             const int64_t*, const int64_t*,
-                             const int32_t*, const int32_t*, int64_t, int,
-                             int64_t*, int64_t*, int64_t*, bool*, int,
-                             hipStream_t);
-void launch_join_build(const int64_t*, int64_t, int32_t*, int32_t*, int64_t,
-                       int32_t*,
-                       hipStream_t);
-void launch_gb_part_hist(const int64_t*, int64_t, int, int64_t*, int,
-                         hipStream_t);
-void launch_reduce_cols(const double*, const bool*, const int32_t*, int,
-                        int64_t, double*, int64_t*, hipStream_t);
-void launch_gb_part_scatter(const int64_t*, const double*, int, int64_t, int,
-                            int64_t*, int64_t*, double*, int, int32_t*,
-                            int64_t, hipStream_t);
-int dense_assign_max();
-void launch_gb_dense_count(const int64_t*, const int64_t*, int, int64_t*,
-                           hipStream_t);
-void launch_gb_dense_assign(const int64_t*, const int64_t*, const int64_t*,
-                            int, int32_t*, int64_t*, int64_t*, hipStream_t);
-void launch_scatter_tile_prep(const int32_t*, int64_t, int, uint16_t*,
-                              int32_t*, hipStream_t);
-void launch_scatter_tile(const double*, const uint16_t*, const int32_t*,
-                         int64_t, int, double*, hipStream_t);
-void launch_gb_dense_aggregate(const int32_t*, const double*, int64_t,
-                               const int64_t*, const int64_t*, int, int64_t,
-                               double*, int64_t, int, hipStream_t);
-void launch_scatter_by_pos(const double*, const int32_t*, int64_t, double*,
-                           hipStream_t);
-void launch_gb_aggregate_part(const int64_t*, const double*, const int32_t*,
-                              int, int64_t, const int64_t*, int64_t, int64_t*,
-                              double*, int64_t*, int64_t, hipStream_t);
-void launch_gb_part_scatter_staged(const int64_t*, const double*, int64_t,
-                                   int, int64_t*, void*, double*, int64_t,
-                                   int, int*, int, hipStream_t);
-void launch_gb_aggregate_part_big(const void*, const double*,
-                                  const int32_t*, int64_t, int64_t*,
-                                  double*, int64_t*, int64_t, int64_t,
-                                  int, int, hipStream_t);
-void launch_gather_cols(const uint64_t*, const uint64_t*, int, int,
-                        const int64_t*, int64_t, hipStream_t);
-void launch_expr_filter(const void*, int64_t, bool*, hipStream_t);
-void launch_expr_value(const void*, int64_t, int, void*, bool*,
-                       hipStream_t);
-void launch_join_count(const int64_t*, int64_t, const int64_t*,
-                       const int64_t*, const int64_t*, const int32_t*,
-                       const int32_t*, int64_t, int32_t*, hipStream_t);
-void launch_join_total(const int64_t*, int64_t, const int64_t*,
-                       const int64_t*, const int64_t*, const int32_t*,
-                       const int32_t*, int64_t, int, int64_t*, hipStream_t);
-void launch_join_emit_chunked(const int64_t*, int64_t, const int64_t*,
-                              const int64_t*, const int64_t*, const int32_t*,
-                              const int32_t*, int64_t, int64_t*, int64_t*,
-                              int64_t*, int, hipStream_t);
-void launch_join_emit(const int64_t*, int64_t, const int64_t*, const int64_t*,
-                      const int64_t*, const int32_t*, const int32_t*, int64_t,
-                      const int64_t*, int64_t*, int64_t*, int, hipStream_t);
-void launch_join_mark_build(const int64_t*, int64_t, const int64_t*,
-                            const int64_t*, const int64_t*, const int32_t*,
-                            const int32_t*, int64_t, bool*, hipStream_t);
-void launch_hash_string_col(const int64_t*, const uint8_t*, const bool*,
-                            uint64_t*, int64_t, int, hipStream_t);
-void launch_hash_seed(uint64_t*, int64_t, uint64_t, hipStream_t);
-void launch_gb_mark_reps(const int64_t*, const int64_t*, const int64_t*,
-                         int64_t, int64_t*, int64_t*, int64_t*, int64_t,
-                         hipStream_t);
-void launch_compact8(const bool*, int64_t, int64_t*, const uint64_t**,
-                     uint64_t**, int, hipStream_t);
-void launch_gb_key_stats(const void**, const bool**, const int*, int,
-                         int64_t, int64_t, int64_t*, int32_t*, int, int,
-                         uint64_t*, hipStream_t);
-void launch_pack_cols(const void**, const bool**, const int*, const int64_t*,
-                      const int*, int, int64_t, int64_t*, hipStream_t);
-void launch_unpack_col(const int64_t*, int64_t, int, int64_t, int64_t, int,
-                       int, void*, bool*, hipStream_t);
-void launch_joinoa_build(const int64_t*, int64_t, int64_t*, int64_t,
-                         int64_t*, hipStream_t);
-void launch_joinoa_probe(const int64_t*, int64_t, const int64_t*, int64_t,
-                         int64_t*, int64_t*, bool*, int, hipStream_t);
-void launch_topk(const void*, int, int, int64_t, int64_t, void*, int64_t*,
-                 void*, int64_t*, hipStream_t);
-void launch_eq2_mask(const int64_t*, const int64_t*, const int64_t*,
-                     const int64_t*, const bool*, int, int64_t, bool*,
-                     hipStream_t);
-void launch_cmp_imm(const void*, const bool*, int, int64_t, double, int,
-                    int, int64_t, bool*, hipStream_t);
-void launch_cmp_col(const void*, const bool*, const void*, const bool*, int,
-                    int, int64_t, bool*, hipStream_t);
-void launch_seg_rank(const int64_t*, const int64_t*, const int64_t* const*,
-                     const uint8_t* const*, const int*, int, int64_t, int,
-                     int64_t*, int64_t*, hipStream_t);
-void launch_seg_take(const int64_t*, const int64_t*, int64_t, int64_t,
-                     int64_t*, int64_t*, int64_t*, int64_t*, hipStream_t);
-int64_t seg_rank_chunk_size();
-void launch_gb_compact(const int64_t*, const int64_t*, const double**,
-                       double**, int, int64_t, int64_t*, int64_t*, int64_t*,
-                       int64_t*, const int64_t*, int64_t*, hipStream_t);
-}
+#include "relational.h"
 
 namespace {
 
@@ -177,7 +62,7 @@ struct GroupTable {
 GroupTable empty_group_table(int64_t n_aggs, int64_t tsize,
                              const at::Tensor& vals) {
   auto kopts = vals.options().dtype(at::kLong);
-  return {at::full({tsize}, (int64_t)0x8000000000000000LL, kopts),
+  return {at::full({tsize}, (int64_t)GB_EMPTY, kopts),
           at::zeros({n_aggs, tsize}, vals.options()),
           at::zeros({tsize}, kopts)};
 }
@@ -289,7 +174,7 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
   TORCH_CHECK((tsize & (tsize - 1)) == 0, "tsize must be a power of 2");
   TORCH_CHECK((num_parts & (num_parts - 1)) == 0,
               "num_parts must be a power of 2");
-  TORCH_CHECK(num_parts <= 4096, "num_parts must be <= 4096");
+  TORCH_CHECK(num_parts <= PART_MAX, "num_parts must be <= ", PART_MAX);
   int64_t n = keys.numel();
   int n_aggs = (int)vals.size(0);
   auto stream = current_stream();
@@ -379,7 +264,7 @@ std::vector<at::Tensor> gb_aggregate_replay(at::Tensor pkeys_cached,
   return {t.tkeys, t.gaggs, t.gcount};
 }
 
-// ---- dense replay (relational.hip "shuffle-layout reuse") ----
+// ---- dense replay (groupby_replay.hip "shuffle-layout reuse") ----
 
 namespace {
 void check_tile(int64_t tile) {
@@ -399,9 +284,9 @@ void check_dense_slots(int64_t slots) {
 std::vector<at::Tensor> gb_dense_count(at::Tensor pkeys, int64_t num_parts) {
   check_gpu(pkeys, "pkeys");
   TORCH_CHECK(pkeys.scalar_type() == at::kLong, "pkeys must be int64");
-  TORCH_CHECK(num_parts >= 1 && num_parts <= 4096 &&
+  TORCH_CHECK(num_parts >= 1 && num_parts <= PART_MAX &&
                   (num_parts & (num_parts - 1)) == 0,
-              "num_parts must be a power of 2 <= 4096");
+              "num_parts must be a power of 2 <= ", PART_MAX);
   auto stream = current_stream();
   auto offsets =
       part_offsets(pkeys, num_parts, part_shift(num_parts), stream);
@@ -731,7 +616,7 @@ std::vector<at::Tensor> gb_mark_reps(at::Tensor h1, at::Tensor h2,
                                      at::Tensor tkeys, int64_t tsize) {
   check_gpu(h1, "h1");
   auto rep = at::full({tsize}, -1, h1.options());
-  auto th2 = at::full({tsize}, (int64_t)0x8000000000000000LL, h1.options());
+  auto th2 = at::full({tsize}, (int64_t)GB_EMPTY, h1.options());
   auto conflict = at::zeros({1}, h1.options());
   if (h1.numel() > 0) {
     launch_gb_mark_reps(h1.data_ptr<int64_t>(), h2.data_ptr<int64_t>(),
@@ -851,12 +736,13 @@ std::vector<at::Tensor> join_open_unique(at::Tensor pkeys, at::Tensor bkeys,
   return {out_pi, out_bi, out_mask, flags};
 }
 
-// Own top-k select for k <= 16 (see relational.hip); returns
+// Own top-k select for k <= 16 (see select.hip); returns
 // (values[k], indices[k]) sorted, index-tiebroken (deterministic).
 std::vector<at::Tensor> topk_select(at::Tensor vals, int64_t k,
                                     bool largest) {
   check_gpu(vals, "vals");
-  TORCH_CHECK(k >= 1 && k <= 16, "k must be in [1, 16]");
+  // checked before k narrows to the launcher's int
+  TORCH_CHECK(k >= 1 && k <= TOPK_MAX, "k must be in [1, ", TOPK_MAX, "]");
   int dt;
   if (vals.scalar_type() == at::kLong) {
     dt = 0;
@@ -867,11 +753,11 @@ std::vector<at::Tensor> topk_select(at::Tensor vals, int64_t k,
   }
   int64_t n = vals.numel();
   TORCH_CHECK(n >= 1, "empty input");
-  auto cand_v = at::empty({512 * k}, vals.options());
-  auto cand_i = at::empty({512 * k}, vals.options().dtype(at::kLong));
+  auto cand_v = at::empty({TOPK_BLOCKS * k}, vals.options());
+  auto cand_i = at::empty({TOPK_BLOCKS * k}, vals.options().dtype(at::kLong));
   auto out_v = at::empty({k}, vals.options());
   auto out_i = at::empty({k}, vals.options().dtype(at::kLong));
-  launch_topk(vals.data_ptr(), dt, largest ? 1 : 0, n, k,
+  launch_topk(vals.data_ptr(), dt, largest ? 1 : 0, n, (int)k,
               cand_v.data_ptr(), cand_i.data_ptr<int64_t>(),
               out_v.data_ptr(), out_i.data_ptr<int64_t>(),
               current_stream());
@@ -891,7 +777,7 @@ at::Tensor eq2_mask(at::Tensor h1, at::Tensor h2, at::Tensor l1,
   return out;
 }
 
-// Fast path for single-comparison WHERE filters (see relational.hip).
+// Fast path for single-comparison WHERE filters (see select.hip).
 at::Tensor cmp_imm(at::Tensor a, c10::optional<at::Tensor> valid,
                    int64_t imm_i, double imm_d, bool use_int, int64_t op) {
   check_gpu(a, "a");
@@ -917,26 +803,15 @@ at::Tensor cmp_col(at::Tensor a, c10::optional<at::Tensor> va, at::Tensor b,
   return out;
 }
 
-// host mirror of ExprProg in relational.hip (layout must match)
-struct ExprProgHost {
-  int n_ops;
-  unsigned char op[48];
-  signed char aux[48];
-  unsigned long long imm[12];
-  unsigned long long col_data[12];
-  unsigned long long col_valid[12];
-  unsigned char col_dt[12];
-};
-
-static ExprProgHost build_expr_prog(at::Tensor& ops, at::Tensor& aux,
-                                    at::Tensor& imm,
-                                    std::vector<at::Tensor>& col_data,
-                                    std::vector<at::Tensor>& col_valid,
-                                    at::Tensor& col_dt) {
-  TORCH_CHECK(ops.numel() <= 48, "program too long");
-  TORCH_CHECK(col_data.size() <= 12, "too many columns");
-  TORCH_CHECK(imm.numel() <= 12, "too many immediates");
-  ExprProgHost prog;
+static ExprProg build_expr_prog(at::Tensor& ops, at::Tensor& aux,
+                                at::Tensor& imm,
+                                std::vector<at::Tensor>& col_data,
+                                std::vector<at::Tensor>& col_valid,
+                                at::Tensor& col_dt) {
+  TORCH_CHECK(ops.numel() <= EXPR_MAX_OPS, "program too long");
+  TORCH_CHECK(col_data.size() <= EXPR_MAX_COLS, "too many columns");
+  TORCH_CHECK(imm.numel() <= EXPR_MAX_COLS, "too many immediates");
+  ExprProg prog;
   std::memset(&prog, 0, sizeof(prog));
   prog.n_ops = (int)ops.numel();
   auto ops_c = ops.to(at::kByte).cpu();
@@ -999,13 +874,14 @@ at::Tensor expr_filter(at::Tensor ops, at::Tensor aux, at::Tensor imm,
 std::vector<at::Tensor> gather_columns(at::Tensor idx,
                                        std::vector<at::Tensor> cols) {
   check_gpu(idx, "idx");
-  TORCH_CHECK(cols.size() >= 1 && cols.size() <= 16, "1..16 columns");
+  TORCH_CHECK(cols.size() >= 1 && cols.size() <= GATHER_MAX_COLS, "1..",
+              GATHER_MAX_COLS, " columns");
   int64_t n = idx.numel();
   // group by element width: one fused launch per width class
   std::vector<at::Tensor> outs(cols.size());
   for (int width : {8, 4, 2, 1}) {
-    uint64_t srcs[16];
-    uint64_t dsts[16];
+    uint64_t srcs[GATHER_MAX_COLS];
+    uint64_t dsts[GATHER_MAX_COLS];
     int k = 0;
     for (size_t c = 0; c < cols.size(); ++c) {
       if (cols[c].element_size() != width) continue;
@@ -1067,12 +943,13 @@ at::Tensor gb_key_stats(std::vector<at::Tensor> cols,
                         std::vector<c10::optional<at::Tensor>> valids,
                         int64_t nsamples, int64_t tsize, bool do_minmax) {
   int k = (int)cols.size();
-  TORCH_CHECK(k >= 1 && k <= 8, "1..8 key columns");
+  TORCH_CHECK(k >= 1 && k <= PACK_MAX_COLS, "1..", PACK_MAX_COLS,
+              " key columns");
   TORCH_CHECK((tsize & (tsize - 1)) == 0, "tsize must be a power of 2");
   int64_t n = cols[0].numel();
-  const void* data[8];
-  const bool* valid[8];
-  int dwidth[8];
+  const void* data[PACK_MAX_COLS];
+  const bool* valid[PACK_MAX_COLS];
+  int dwidth[PACK_MAX_COLS];
   for (int c = 0; c < k; ++c) {
     check_gpu(cols[c], "key col");
     int es = (int)cols[c].element_size();
@@ -1099,12 +976,13 @@ at::Tensor pack_columns(std::vector<at::Tensor> cols,
                         std::vector<int64_t> mins,
                         std::vector<int64_t> shifts) {
   int k = (int)cols.size();
-  TORCH_CHECK(k >= 1 && k <= 8, "1..8 key columns");
+  TORCH_CHECK(k >= 1 && k <= PACK_MAX_COLS, "1..", PACK_MAX_COLS,
+              " key columns");
   int64_t n = cols[0].numel();
-  const void* data[8];
-  const bool* valid[8];
-  int dwidth[8];
-  int shift_i[8];
+  const void* data[PACK_MAX_COLS];
+  const bool* valid[PACK_MAX_COLS];
+  int dwidth[PACK_MAX_COLS];
+  int shift_i[PACK_MAX_COLS];
   for (int c = 0; c < k; ++c) {
     check_gpu(cols[c], "key col");
     int es = (int)cols[c].element_size();
@@ -1154,16 +1032,16 @@ std::vector<at::Tensor> gb_compact(at::Tensor tkeys, at::Tensor gcount,
   check_gpu(gcount, "gcount");
   int64_t tsize = tkeys.numel();
   int n_aggs = gaggs.numel() > 0 ? (int)gaggs.size(0) : 0;
-  TORCH_CHECK(n_aggs <= 6, "at most 6 aggregate columns");
-  const int64_t chunk = 256 * 32;
-  int64_t nblocks = (tsize + chunk - 1) / chunk;
+  TORCH_CHECK(n_aggs <= GBC_MAX_AGGS, "at most ", GBC_MAX_AGGS,
+              " aggregate columns");
+  int64_t nblocks = (tsize + GBC_CHUNK - 1) / GBC_CHUNK;
   auto bcounts = at::empty({nblocks}, tkeys.options());
   auto bases = at::empty({nblocks + 1}, tkeys.options());
   auto out_keys = at::empty({tsize}, tkeys.options());
   auto out_count = at::empty({tsize}, gcount.options());
   at::Tensor out_aggs = at::empty({n_aggs, tsize}, gaggs.options());
-  const double* asrc[6];
-  double* adst[6];
+  const double* asrc[GBC_MAX_AGGS];
+  double* adst[GBC_MAX_AGGS];
   for (int a = 0; a < n_aggs; ++a) {
     asrc[a] = gaggs[a].data_ptr<double>();
     adst[a] = out_aggs[a].data_ptr<double>();
@@ -1191,7 +1069,7 @@ std::vector<at::Tensor> gb_compact(at::Tensor tkeys, at::Tensor gcount,
 // row lands at its ORIGINAL row position.  kind 0 row_number, 1 rank,
 // 2 dense_rank.  Order columns are 8-byte (int64 bits or float64) in
 // original row order, each with an optional bool validity tensor.
-int64_t seg_rank_chunk() { return seg_rank_chunk_size(); }
+int64_t seg_rank_chunk() { return SEG_CHUNK; }
 
 static void seg_check_inputs(const at::Tensor& perm, const at::Tensor& pkeys) {
   check_gpu(perm, "perm");
@@ -1210,12 +1088,13 @@ at::Tensor seg_rank(at::Tensor perm, at::Tensor pkeys,
   seg_check_inputs(perm, pkeys);
   int64_t n = perm.numel();
   int ncols = (int)col_data.size();
-  TORCH_CHECK(ncols <= 4, "at most 4 order columns");
+  TORCH_CHECK(ncols <= SEG_MAX_COLS, "at most ", SEG_MAX_COLS,
+              " order columns");
   TORCH_CHECK(col_valid.size() == col_data.size(), "col_valid size mismatch");
   TORCH_CHECK(kind >= 0 && kind <= 2, "kind must be 0, 1 or 2");
-  const int64_t* cd[4] = {nullptr, nullptr, nullptr, nullptr};
-  const uint8_t* cv[4] = {nullptr, nullptr, nullptr, nullptr};
-  int cf[4] = {0, 0, 0, 0};
+  const int64_t* cd[SEG_MAX_COLS] = {};
+  const uint8_t* cv[SEG_MAX_COLS] = {};
+  int cf[SEG_MAX_COLS] = {};
   for (int c = 0; c < ncols; ++c) {
     check_gpu(col_data[c], "order column");
     TORCH_CHECK(col_data[c].is_contiguous() && col_data[c].numel() == n &&
@@ -1234,8 +1113,7 @@ at::Tensor seg_rank(at::Tensor perm, at::Tensor pkeys,
   }
   auto out = at::empty({n}, perm.options());
   if (n == 0) return out;
-  int64_t chunk = seg_rank_chunk_size();
-  int64_t nblocks = (n + chunk - 1) / chunk;
+  int64_t nblocks = (n + SEG_CHUNK - 1) / SEG_CHUNK;
   auto work = at::empty({6 * nblocks}, perm.options());
   launch_seg_rank(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(), cd, cv,
                   cf, ncols, n, (int)kind, work.data_ptr<int64_t>(),
@@ -1250,8 +1128,7 @@ std::vector<at::Tensor> seg_take(at::Tensor perm, at::Tensor pkeys,
                                  int64_t n_take) {
   seg_check_inputs(perm, pkeys);
   int64_t n = perm.numel();
-  int64_t chunk = seg_rank_chunk_size();
-  int64_t nblocks = (n + chunk - 1) / chunk;
+  int64_t nblocks = (n + SEG_CHUNK - 1) / SEG_CHUNK;
   auto out = at::empty({n}, perm.options());
   if (n == 0) return {out, at::zeros({1}, perm.options())};
   auto work = at::empty({6 * nblocks}, perm.options());
@@ -1284,7 +1161,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tsize"), py::arg("scatter_chunk"), py::arg("agg_chunk"),
         py::arg("narrow"), py::arg("record_layout"),
         py::arg("force_simple"), py::arg("record_chunk") = 0);
-  m.def("dense_assign_max", []() { return (int64_t)dense_assign_max(); },
+  m.def("dense_assign_max", []() { return (int64_t)DENSE_ASSIGN_MAX; },
         "largest per-partition distinct count the dense layout accepts");
   m.def("gb_dense_count", &gb_dense_count,
         "dense replay preparation: offsets + distinct keys per partition",

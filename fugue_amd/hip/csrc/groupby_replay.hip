@@ -1,0 +1,397 @@
+// Group-by replay family: re-aggregation over a recorded shuffle layout.
+#include <hip/hip_runtime.h>
+
+#include "device_common.h"
+#include "relational.h"
+
+// ------------------------------------------------------------------ //
+// shuffle-layout reuse (Spark shuffle-reuse analog)                   //
+//                                                                     //
+// Re-aggregating the SAME key column with fresh values (iterative     //
+// pipelines) skips hist + key scatter entirely.  Two replay forms:    //
+//                                                                     //
+//  * plain replay (any single aggregate): the recorded per-row spill  //
+//    position places the new values (scatter_by_pos_kernel) and the   //
+//    cached partitioned keys feed phase 3 unchanged.                  //
+//  * dense replay (single SUM over a null-free fp64 column): with the //
+//    keys fixed, the set of groups, their counts, their output order  //
+//    and each row's group are fixed too.  They are computed ONCE when //
+//    the layout is recorded (gb_dense_count/assign kernels: a dense   //
+//    int32 group id per partitioned row, partition-major and          //
+//    key-ascending inside a partition, plus the output keys/counts),  //
+//    so a replayed step is the tile-coalesced value scatter           //
+//    (scatter_tile_kernel) and one LDS f64 add per row                //
+//    (gb_dense_aggregate_kernel): no keys, hashing, CAS, counting,    //
+//    table fills, compaction or host readback.                        //
+// ------------------------------------------------------------------ //
+
+__global__ __launch_bounds__(BLOCK) void scatter_by_pos_kernel(
+    const double* __restrict__ vals, const int32_t* __restrict__ pos,
+    int64_t n, double* __restrict__ out_vals) {
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    out_vals[pos[i]] = vals[i];
+  }
+}
+
+extern "C" {
+void launch_scatter_by_pos(const double* vals, const int32_t* pos, int64_t n,
+                           double* out_vals, hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_by_pos_kernel, dim3(grid_for(n, 2)), dim3(BLOCK),
+                     0, stream, vals, pos, n, out_vals);
+}
+}  // extern "C"
+
+
+// ------------------------------------------------------------------ //
+// dense replay: one-time preparation                                  //
+// ------------------------------------------------------------------ //
+
+// LDS table used to assign ids inside one partition; a partition with
+// more than DENSE_ASSIGN_MAX distinct keys declines the dense layout
+// (the caller keeps the plain replay).  The racy capacity check can
+// overshoot by one insert per thread, which still leaves the table
+// far from full, so probing always terminates.
+#define DENSE_ASSIGN_SLOTS 4096
+#define DENSE_ASSIGN_POISON (1 << 20)
+
+// in-place ascending bitonic sort of n (power of 2) LDS elements by the
+// whole block; ends with a barrier
+template <typename T>
+__device__ __forceinline__ void lds_bitonic_sort(T* x, int n) {
+  for (int k = 2; k <= n; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
+        int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        int l = i | j;
+        bool up = (i & k) == 0;
+        T a = x[i], b = x[l];
+        if ((a > b) == up) {
+          x[i] = b;
+          x[l] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// distinct keys of rows [lo, hi) into the LDS set lkeys (pre-filled
+// with GB_EMPTY); *ndist counts them.  A key equal to the sentinel
+// poisons the count so that the partition is declined.
+__device__ __forceinline__ void dense_insert_keys(
+    const int64_t* __restrict__ pkeys, int64_t lo, int64_t hi,
+    int64_t* __restrict__ lkeys, int* __restrict__ ndist) {
+  for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    int64_t key = pkeys[i];
+    if (key == GB_EMPTY) {
+      atomicAdd(ndist, DENSE_ASSIGN_POISON);
+      continue;
+    }
+    int slot = (int)(mix64((uint64_t)key) & (DENSE_ASSIGN_SLOTS - 1));
+    for (int probe = 0; probe < DENSE_ASSIGN_SLOTS; ++probe) {
+      int64_t cur = lkeys[slot];
+      if (cur == key) break;
+      if (cur == GB_EMPTY) {
+        if (*(volatile int*)ndist > DENSE_ASSIGN_MAX) break;  // declined
+        int64_t prev = (int64_t)lds_key_cas(&lkeys[slot], (int64_t)GB_EMPTY, key);
+        if (prev == GB_EMPTY) {
+          atomicAdd(ndist, 1);
+          break;
+        }
+        if (prev == key) break;
+      }
+      slot = (slot + 1) & (DENSE_ASSIGN_SLOTS - 1);
+    }
+  }
+}
+
+// pass 1: distinct keys per partition (one block per partition)
+__global__ __launch_bounds__(BLOCK) void gb_dense_count_kernel(
+    const int64_t* __restrict__ pkeys, const int64_t* __restrict__ offsets,
+    int num_parts, int64_t* __restrict__ distinct) {
+  __shared__ int64_t lkeys[DENSE_ASSIGN_SLOTS];
+  __shared__ int ndist;
+  for (int p = blockIdx.x; p < num_parts; p += gridDim.x) {
+    for (int i = threadIdx.x; i < DENSE_ASSIGN_SLOTS; i += blockDim.x)
+      lkeys[i] = GB_EMPTY;
+    if (threadIdx.x == 0) ndist = 0;
+    __syncthreads();
+    dense_insert_keys(pkeys, offsets[p], offsets[p + 1], lkeys, &ndist);
+    __syncthreads();
+    if (threadIdx.x == 0) distinct[p] = ndist;
+    __syncthreads();
+  }
+}
+
+// pass 2 (only when no partition was declined): sort the partition's
+// distinct keys, id = group_base[p] + rank of the key; writes the dense
+// id of every partitioned row and the output keys/counts in id order
+__global__ __launch_bounds__(BLOCK) void gb_dense_assign_kernel(
+    const int64_t* __restrict__ pkeys, const int64_t* __restrict__ offsets,
+    const int64_t* __restrict__ group_base, int num_parts,
+    int32_t* __restrict__ gid, int64_t* __restrict__ out_keys,
+    int64_t* __restrict__ out_count) {
+  __shared__ int64_t lkeys[DENSE_ASSIGN_SLOTS];
+  __shared__ int lcount[DENSE_ASSIGN_MAX];
+  __shared__ int ndist;
+  for (int p = blockIdx.x; p < num_parts; p += gridDim.x) {
+    for (int i = threadIdx.x; i < DENSE_ASSIGN_SLOTS; i += blockDim.x)
+      lkeys[i] = GB_EMPTY;
+    for (int i = threadIdx.x; i < DENSE_ASSIGN_MAX; i += blockDim.x)
+      lcount[i] = 0;
+    if (threadIdx.x == 0) ndist = 0;
+    __syncthreads();
+    int64_t lo = offsets[p], hi = offsets[p + 1];
+    dense_insert_keys(pkeys, lo, hi, lkeys, &ndist);
+    __syncthreads();
+    int d = ndist;
+    if (d > DENSE_ASSIGN_MAX) d = 0;  // not reached: pass 1 declined
+    // GB_EMPTY is INT64_MIN: empties sort first, keys fill the tail
+    lds_bitonic_sort<int64_t>(lkeys, DENSE_ASSIGN_SLOTS);
+    const int64_t* sorted = lkeys + (DENSE_ASSIGN_SLOTS - d);
+    int64_t gb = group_base[p];
+    if (d > 0) {
+      for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+        int64_t key = pkeys[i];
+        int a = 0, b = d - 1;  // key is present: lower bound
+        while (a < b) {
+          int mid = (a + b) >> 1;
+          if (sorted[mid] < key) a = mid + 1; else b = mid;
+        }
+        gid[i] = (int32_t)(gb + a);
+        atomicAdd(&lcount[a], 1);
+      }
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < d; r += blockDim.x) {
+      out_keys[gb + r] = sorted[r];
+      out_count[gb + r] = lcount[r];
+    }
+    __syncthreads();
+  }
+}
+
+// Tile-coalesced value scatter, preparation: per tile of C input rows,
+// sort the rows by destination.  rank[i] = tile-local rank of row i,
+// dst[tile*C + r] = destination of the tile's r-th ranked row.  Works
+// for any permutation `pos`; with a layout recorded at a reservation
+// chunk equal to C, the rows of one (tile, partition) are consecutive
+// ranks with consecutive destinations.
+__global__ __launch_bounds__(BLOCK) void scatter_tile_prep_kernel(
+    const int32_t* __restrict__ pos, int64_t n, int C,
+    uint16_t* __restrict__ rank, int32_t* __restrict__ dst) {
+  extern __shared__ unsigned long long tile_sort[];
+  int64_t ntiles = (n + C - 1) / C;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t t0 = tile * C;
+    int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+    for (int i = threadIdx.x; i < C; i += blockDim.x) {
+      tile_sort[i] = i < cnt ? (((unsigned long long)(uint32_t)pos[t0 + i]
+                                 << 16) | (unsigned long long)i)
+                             : ~0ULL;
+    }
+    __syncthreads();
+    lds_bitonic_sort<unsigned long long>(tile_sort, C);
+    for (int r = threadIdx.x; r < cnt; r += blockDim.x) {
+      unsigned long long e = tile_sort[r];
+      dst[t0 + r] = (int32_t)(e >> 16);
+      rank[t0 + (int)(e & 0xffffULL)] = (uint16_t)r;
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------ //
+// dense replay: per-step kernels                                      //
+// ------------------------------------------------------------------ //
+
+// out[dst[tile*C + r]] = value of the tile's r-th ranked row: values are
+// loaded coalesced, permuted through LDS, and leave with consecutive
+// lanes on consecutive ranks, so the rows of one (tile, partition) run
+// are one contiguous segment instead of isolated 8-byte stores.
+__global__ __launch_bounds__(BLOCK) void scatter_tile_kernel(
+    const double* __restrict__ vals, const uint16_t* __restrict__ rank,
+    const int32_t* __restrict__ dst, int64_t n, int C,
+    double* __restrict__ out) {
+  extern __shared__ double tile_vals[];
+  int64_t ntiles = (n + C - 1) / C;
+  const int stride = blockDim.x;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t t0 = tile * C;
+    int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+    const double* tv = vals + t0;
+    const uint16_t* tr = rank + t0;
+    int i = threadIdx.x;
+    for (; i + 3 * stride < cnt; i += 4 * stride) {
+      double v[4];
+      int r[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = tv[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) r[u] = tr[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (r[u] < cnt) tile_vals[r[u]] = v[u];
+    }
+    for (; i < cnt; i += stride) {
+      int r = tr[i];
+      if (r < cnt) tile_vals[r] = tv[i];
+    }
+    __syncthreads();
+    const int32_t* td = dst + t0;
+    i = threadIdx.x;
+    for (; i + 3 * stride < cnt; i += 4 * stride) {
+      int64_t d[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) d[u] = td[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if ((uint64_t)d[u] < (uint64_t)n) out[d[u]] = tile_vals[i + u * stride];
+    }
+    for (; i < cnt; i += stride) {
+      int64_t d = td[i];
+      if ((uint64_t)d < (uint64_t)n) out[d] = tile_vals[i];
+    }
+    __syncthreads();
+  }
+}
+
+// Dense replay aggregate: one LDS f64 add per row into a table indexed
+// by gid - base, base = first id of the partition holding the chunk's
+// first row.  Ids of one partition are contiguous and partitions are in
+// id order, so a chunk's ids start at base; a row whose id falls past
+// the table (chunk spanning more partitions than the table covers) adds
+// straight to out_sum.  Correct for ANY chunk/partition geometry.
+// LDS per block is SLOTS*8 B: 2048 -> 16KB, 4096 -> 32KB, 8192 -> 64KB.
+template <int SLOTS>
+__global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_kernel(
+    const int32_t* __restrict__ gid, const double* __restrict__ part_vals,
+    int64_t n, const int64_t* __restrict__ offsets,
+    const int64_t* __restrict__ group_base, int num_parts, int64_t n_groups,
+    double* __restrict__ out_sum, int64_t chunk) {
+  __shared__ double lsum[SLOTS];
+  __shared__ int sbase;
+  for (int64_t start = (int64_t)blockIdx.x * chunk; start < n;
+       start += (int64_t)gridDim.x * chunk) {
+    int64_t end = start + chunk;
+    if (end > n) end = n;
+    for (int i = threadIdx.x; i < SLOTS; i += blockDim.x) lsum[i] = 0.0;
+    if (threadIdx.x == 0) {
+      // largest p with offsets[p] <= start (skips empty partitions)
+      int lo = 0, hi = num_parts;
+      while (hi - lo > 1) {
+        int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= start) lo = mid; else hi = mid;
+      }
+      sbase = (int)group_base[lo];
+    }
+    __syncthreads();
+    const int base = sbase;
+    int64_t i = start + threadIdx.x;
+    const int64_t stride = (int64_t)blockDim.x;
+    for (; i + 3 * stride < end; i += 4 * stride) {
+      int g[4];
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) g[u] = gid[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = part_vals[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        unsigned rel = (unsigned)(g[u] - base);
+        if (rel < (unsigned)SLOTS) {
+          atomicAdd(&lsum[rel], v[u]);
+        } else if ((uint64_t)g[u] < (uint64_t)n_groups) {
+          atomicAdd(&out_sum[g[u]], v[u]);
+        }
+      }
+    }
+    for (; i < end; i += stride) {
+      int g = gid[i];
+      double v = part_vals[i];
+      unsigned rel = (unsigned)(g - base);
+      if (rel < (unsigned)SLOTS) {
+        atomicAdd(&lsum[rel], v);
+      } else if ((uint64_t)g < (uint64_t)n_groups) {
+        atomicAdd(&out_sum[g], v);
+      }
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < SLOTS; s += blockDim.x) {
+      double v = lsum[s];
+      if (v != 0.0 && (int64_t)base + s < n_groups)
+        atomicAdd(&out_sum[(int64_t)base + s], v);
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" {
+
+void launch_gb_dense_count(const int64_t* pkeys, const int64_t* offsets,
+                           int num_parts, int64_t* distinct,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(gb_dense_count_kernel, dim3(num_parts), dim3(BLOCK), 0,
+                     stream, pkeys, offsets, num_parts, distinct);
+}
+
+void launch_gb_dense_assign(const int64_t* pkeys, const int64_t* offsets,
+                            const int64_t* group_base, int num_parts,
+                            int32_t* gid, int64_t* out_keys,
+                            int64_t* out_count, hipStream_t stream) {
+  hipLaunchKernelGGL(gb_dense_assign_kernel, dim3(num_parts), dim3(BLOCK), 0,
+                     stream, pkeys, offsets, group_base, num_parts, gid,
+                     out_keys, out_count);
+}
+
+// tile must be a power of 2 in [512, 8192]: the value tile (tile*8 B of
+// LDS) then stays within the 64KB a block gets without opting in
+void launch_scatter_tile_prep(const int32_t* pos, int64_t n, int tile,
+                              uint16_t* rank, int32_t* dst,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_tile_prep_kernel, dim3(chunk_grid(n, tile)),
+                     dim3(BLOCK), (size_t)tile * sizeof(unsigned long long),
+                     stream, pos, n, tile, rank, dst);
+}
+
+void launch_scatter_tile(const double* vals, const uint16_t* rank,
+                         const int32_t* dst, int64_t n, int tile,
+                         double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_tile_kernel, dim3(chunk_grid(n, tile)),
+                     dim3(BLOCK), (size_t)tile * sizeof(double), stream, vals,
+                     rank, dst, n, tile, out);
+}
+
+void launch_gb_dense_aggregate(const int32_t* gid, const double* part_vals,
+                               int64_t n, const int64_t* offsets,
+                               const int64_t* group_base, int num_parts,
+                               int64_t n_groups, double* out_sum,
+                               int64_t chunk, int slots,
+                               hipStream_t stream) {
+  // sweep on the 125M-row bench shape (ms per call, profiles/NOTES.md
+  // r03): 4096 slots 0.310/0.296/0.284/0.278/0.278 at 4K/8K/16K/32K/64K
+  // rows per chunk; 2048 slots the same within 2%; 8192 slots slower
+  // below 64K (0.488 at 4K)
+  if (chunk <= 0) chunk = BLOCK * 128;
+  dim3 g(chunk_grid(n, chunk)), b(BLOCK);
+  switch (slots) {
+    case 2048:
+      hipLaunchKernelGGL((gb_dense_aggregate_kernel<2048>), g, b, 0, stream,
+                         gid, part_vals, n, offsets, group_base, num_parts,
+                         n_groups, out_sum, chunk);
+      break;
+    case 8192:
+      hipLaunchKernelGGL((gb_dense_aggregate_kernel<8192>), g, b, 0, stream,
+                         gid, part_vals, n, offsets, group_base, num_parts,
+                         n_groups, out_sum, chunk);
+      break;
+    default:
+      hipLaunchKernelGGL((gb_dense_aggregate_kernel<4096>), g, b, 0, stream,
+                         gid, part_vals, n, offsets, group_base, num_parts,
+                         n_groups, out_sum, chunk);
+  }
+}
+
+}  // extern "C"

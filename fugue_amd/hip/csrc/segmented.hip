@@ -1,0 +1,554 @@
+// Block-scan family: order-preserving pipelines built on per-block counts
+// and the single-block scan gbc_scan_kernel, which both share: the
+// group-table compaction and the segmented rank / take.
+#include <hip/hip_runtime.h>
+
+#include "device_common.h"
+#include "relational.h"
+
+// ------------------------------------------------------------------ //
+// deterministic group-table compaction                                //
+//                                                                     //
+// Replaces occupied = (tkeys != EMPTY).nonzero() + per-column          //
+// index_select with a 3-kernel own pipeline (count / scan / emit) that //
+// preserves slot order (deterministic output) and moves each byte      //
+// once.  total lands in bases[nblocks] for a single host read.         //
+// ------------------------------------------------------------------ //
+
+__global__ __launch_bounds__(BLOCK) void gbc_count_kernel(
+    const int64_t* __restrict__ tkeys, int64_t tsize,
+    int64_t* __restrict__ bcounts) {
+  __shared__ int lcount;
+  int64_t start = (int64_t)blockIdx.x * GBC_CHUNK;
+  if (threadIdx.x == 0) lcount = 0;
+  __syncthreads();
+  int64_t end = start + GBC_CHUNK < tsize ? start + GBC_CHUNK : tsize;
+  int local = 0;
+  for (int64_t i = start + threadIdx.x; i < end; i += blockDim.x)
+    if (tkeys[i] != GB_EMPTY) ++local;
+  atomicAdd(&lcount, local);
+  __syncthreads();
+  if (threadIdx.x == 0) bcounts[blockIdx.x] = lcount;
+}
+
+// single-block exclusive scan of bcounts (nblocks <= 65536); writes the
+// total into bases[nblocks]
+__global__ __launch_bounds__(BLOCK) void gbc_scan_kernel(
+    const int64_t* __restrict__ bcounts, int nblocks,
+    int64_t* __restrict__ bases) {
+  __shared__ int64_t carry;
+  __shared__ int64_t tile[BLOCK];
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int t0 = 0; t0 < nblocks; t0 += BLOCK) {
+    int i = t0 + threadIdx.x;
+    int64_t v = i < nblocks ? bcounts[i] : 0;
+    tile[threadIdx.x] = v;
+    __syncthreads();
+    // inclusive scan in LDS
+    for (int off = 1; off < BLOCK; off <<= 1) {
+      int64_t add = threadIdx.x >= off ? tile[threadIdx.x - off] : 0;
+      __syncthreads();
+      tile[threadIdx.x] += add;
+      __syncthreads();
+    }
+    if (i < nblocks) bases[i] = carry + tile[threadIdx.x] - v;  // exclusive
+    __syncthreads();
+    if (threadIdx.x == 0) carry += tile[BLOCK - 1];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) bases[nblocks] = carry;  // total
+}
+
+struct GbcAggs {
+  const double* src[GBC_MAX_AGGS];
+  double* dst[GBC_MAX_AGGS];
+};
+
+__global__ __launch_bounds__(BLOCK) void gbc_emit_kernel(
+    const int64_t* __restrict__ tkeys, const int64_t* __restrict__ gcount,
+    GbcAggs ag, int n_aggs, int64_t tsize,
+    const int64_t* __restrict__ bases, int64_t* __restrict__ out_keys,
+    int64_t* __restrict__ out_count, const int64_t* __restrict__ extra_src,
+    int64_t* __restrict__ extra_dst) {
+  __shared__ int64_t wbase[BLOCK / WAVE];
+  __shared__ int64_t sbase;
+  int64_t start = (int64_t)blockIdx.x * GBC_CHUNK;
+  int64_t end = start + GBC_CHUNK < tsize ? start + GBC_CHUNK : tsize;
+  if (threadIdx.x == 0) sbase = bases[blockIdx.x];
+  int wave = threadIdx.x / WAVE;
+  int lane = threadIdx.x % WAVE;
+  __syncthreads();
+  for (int64_t i0 = start; i0 < end; i0 += blockDim.x) {
+    int64_t i = i0 + threadIdx.x;
+    bool occ = i < end && tkeys[i] != GB_EMPTY;
+    uint64_t mask = __ballot(occ);
+    int rank = __popcll(mask & ((1ULL << lane) - 1ULL));
+    if (lane == 0) wbase[wave] = __popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int64_t acc = sbase;
+      for (int w = 0; w < BLOCK / WAVE; ++w) {
+        int64_t c = wbase[w];
+        wbase[w] = acc;
+        acc += c;
+      }
+      sbase = acc;
+    }
+    __syncthreads();
+    if (occ) {
+      int64_t pos = wbase[wave] + rank;
+      out_keys[pos] = tkeys[i];
+      out_count[pos] = gcount[i];
+      if (extra_src != nullptr) extra_dst[pos] = extra_src[i];
+      for (int a = 0; a < n_aggs; ++a) ag.dst[a][pos] = ag.src[a][i];
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" {
+
+void launch_gb_compact(const int64_t* tkeys, const int64_t* gcount,
+                       const double** agg_src, double** agg_dst, int n_aggs,
+                       int64_t tsize, int64_t* bcounts, int64_t* bases,
+                       int64_t* out_keys, int64_t* out_count,
+                       const int64_t* extra_src, int64_t* extra_dst,
+                       hipStream_t stream) {
+  int nblocks = (int)((tsize + GBC_CHUNK - 1) / GBC_CHUNK);
+  hipLaunchKernelGGL(gbc_count_kernel, dim3(nblocks), dim3(BLOCK), 0, stream,
+                     tkeys, tsize, bcounts);
+  hipLaunchKernelGGL(gbc_scan_kernel, dim3(1), dim3(BLOCK), 0, stream,
+                     bcounts, nblocks, bases);
+  GbcAggs ag;
+  memset(&ag, 0, sizeof(ag));
+  for (int a = 0; a < n_aggs; ++a) {
+    ag.src[a] = agg_src[a];
+    ag.dst[a] = agg_dst[a];
+  }
+  hipLaunchKernelGGL(gbc_emit_kernel, dim3(nblocks), dim3(BLOCK), 0, stream,
+                     tkeys, gcount, ag, n_aggs, tsize, bases, out_keys,
+                     out_count, extra_src, extra_dst);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ //
+// segmented rank over a sorted permutation                            //
+//                                                                     //
+// perm is a stable sort permutation by (partition key, order keys);   //
+// pkeys and the order columns stay in original row order and are      //
+// gathered through perm.  Sorted position i carries a head flag (new  //
+// partition) and a peer flag (new partition or any order column       //
+// differs from position i-1).  From those:                            //
+//   row_number = i - seg_start + 1                                    //
+//   rank       = peer_start - seg_start + 1                           //
+//   dense_rank = #peer flags in [seg_start, i]                        //
+// Window mode scatters the rank to out[perm[i]] (original row order); //
+// take mode keeps row_number <= n_take and emits the kept perm values //
+// in sorted order through count -> gbc_scan_kernel -> emit.           //
+//                                                                     //
+// Chunks of SEG_CHUNK positions are chained by separate launches      //
+// (summary -> single-block scan -> apply): no block ever waits for    //
+// another block inside a launch.                                      //
+// ------------------------------------------------------------------ //
+
+#define SEG_ITERS (SEG_CHUNK / BLOCK)
+#define SEG_WAVES (BLOCK / WAVE)
+
+struct SegCols {
+  const int64_t* data[SEG_MAX_COLS];   // 8-byte values, original row order
+  const uint8_t* valid[SEG_MAX_COLS];  // optional validity, nullptr = all
+  int is_float[SEG_MAX_COLS];          // compare as double (NaN == NaN)
+};
+
+// (last head position, last peer position, peer flags since that head)
+// of a range of sorted positions; seg < 0 means the range has no head
+// and cnt counts every peer flag of the range.
+struct SegAgg {
+  int64_t seg;
+  int64_t peer;
+  int64_t cnt;
+};
+
+__device__ __forceinline__ SegAgg seg_combine(SegAgg a, SegAgg b) {
+  SegAgg r;
+  r.seg = b.seg >= 0 ? b.seg : a.seg;
+  r.peer = b.peer >= 0 ? b.peer : a.peer;
+  r.cnt = b.seg >= 0 ? b.cnt : a.cnt + b.cnt;
+  return r;
+}
+
+__device__ __forceinline__ int64_t seg_row(const int64_t* __restrict__ perm,
+                                           int64_t i, int64_t n) {
+  int64_t j = perm[i];
+  // a malformed permutation must not read or write out of bounds
+  return (uint64_t)j < (uint64_t)n ? j : 0;
+}
+
+// head/peer flags of sorted position i.  Neighbouring lanes hand their
+// gathered values down with a shuffle; lane 0 fetches its predecessor.
+// Must be called by every lane of the wave.
+__device__ __forceinline__ void seg_flags(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const SegCols& oc, int ncols, int64_t i, int64_t n, int lane, int64_t& j,
+    bool& h, bool& p) {
+  bool in = i < n;
+  j = in ? seg_row(perm, i, n) : 0;
+  bool fetch_prev = in && lane == 0 && i > 0;
+  int64_t jp = fetch_prev ? seg_row(perm, i - 1, n) : 0;
+  int64_t k = in ? pkeys[j] : 0;
+  int64_t kp = __shfl_up(k, 1);
+  if (fetch_prev) kp = pkeys[jp];
+  h = in && (i == 0 || k != kp);
+  bool diff = false;
+  for (int c = 0; c < ncols; ++c) {
+    const int64_t* d = oc.data[c];
+    const uint8_t* vd = oc.valid[c];
+    int64_t v = in ? d[j] : 0;
+    int ok = (in && vd != nullptr) ? (int)(vd[j] != 0) : 1;
+    int64_t vp = __shfl_up(v, 1);
+    int okp = __shfl_up(ok, 1);
+    if (fetch_prev) {
+      vp = d[jp];
+      okp = vd != nullptr ? (int)(vd[jp] != 0) : 1;
+    }
+    bool eq;
+    if (ok && okp) {
+      if (oc.is_float[c]) {
+        double a = __longlong_as_double(v), b = __longlong_as_double(vp);
+        eq = a == b || (a != a && b != b);
+      } else {
+        eq = v == vp;
+      }
+    } else {
+      eq = ok == okp;  // null/null equal, null/value different
+    }
+    diff |= !eq;
+  }
+  p = in && (h || diff);
+}
+
+__device__ __forceinline__ int seg_top_bit(uint64_t m) {
+  return 63 - __clzll((long long)m);
+}
+
+// Resolve (seg_start, peer_start, dense count) of this lane's position
+// from the block's flags.  carry is the aggregate of everything before
+// this iteration's 256 positions and is advanced past them; ws is the
+// LDS exchange buffer of this iteration's parity (double-buffered by the
+// caller, so one barrier per call is enough).  Block-uniform call.
+__device__ __forceinline__ SegAgg seg_block_step(bool h, bool p, int64_t i0,
+                                                 int lane, int wave,
+                                                 SegAgg& carry, SegAgg* ws) {
+  uint64_t hmask = __ballot(h);
+  uint64_t pmask = __ballot(p);
+  int64_t w0 = i0 + (int64_t)wave * WAVE;
+  if (lane == 0) {
+    SegAgg s;
+    if (hmask != 0) {
+      int hb = seg_top_bit(hmask);
+      s.seg = w0 + hb;
+      s.cnt = __popcll(pmask >> hb);
+    } else {
+      s.seg = -1;
+      s.cnt = __popcll(pmask);
+    }
+    s.peer = pmask != 0 ? w0 + seg_top_bit(pmask) : -1;
+    ws[wave] = s;
+  }
+  __syncthreads();
+  SegAgg in = carry;
+  SegAgg tot = carry;
+#pragma unroll
+  for (int w = 0; w < SEG_WAVES; ++w) {
+    SegAgg s = ws[w];
+    if (w < wave) in = seg_combine(in, s);
+    tot = seg_combine(tot, s);
+  }
+  carry = tot;
+  uint64_t le = (2ULL << lane) - 1ULL;  // lanes <= this one
+  uint64_t mh = hmask & le, mp = pmask & le;
+  SegAgg r;
+  if (mh != 0) {
+    int hb = seg_top_bit(mh);
+    r.seg = w0 + hb;
+    r.cnt = __popcll(mp >> hb);
+  } else {
+    r.seg = in.seg;
+    r.cnt = in.cnt + __popcll(mp);
+  }
+  r.peer = mp != 0 ? w0 + seg_top_bit(mp) : in.peer;
+  return r;
+}
+
+// per-chunk aggregate of the flags
+__global__ __launch_bounds__(BLOCK) void seg_rank_summary_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    SegCols oc, int ncols, int64_t n, int64_t* __restrict__ sum_seg,
+    int64_t* __restrict__ sum_peer, int64_t* __restrict__ sum_cnt) {
+  __shared__ int s_head, s_peer, s_cnt;
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  if (threadIdx.x == 0) {
+    s_head = -1;
+    s_peer = -1;
+    s_cnt = 0;
+  }
+  __syncthreads();
+  uint32_t pbits = 0;
+  int lhead = -1, lpeer = -1;
+#pragma unroll 4
+  for (int it = 0; it < SEG_ITERS; ++it) {
+    int rel = it * BLOCK + (int)threadIdx.x;
+    int64_t i = start + rel;
+    if (start + (int64_t)it * BLOCK >= n) break;  // block-uniform
+    int64_t j;
+    bool h, p;
+    seg_flags(perm, pkeys, oc, ncols, i, n, lane, j, h, p);
+    if (h) lhead = rel;
+    if (p) {
+      lpeer = rel;
+      pbits |= 1u << it;
+    }
+  }
+  if (lhead >= 0) atomicMax(&s_head, lhead);
+  if (lpeer >= 0) atomicMax(&s_peer, lpeer);
+  __syncthreads();
+  int bhead = s_head;
+  // peer flags at or after the chunk's last head (all of them if none):
+  // this thread's positions are it*BLOCK + tid
+  int local = 0;
+  if (bhead < 0) {
+    local = __popc(pbits);
+  } else {
+    int it0 = bhead / BLOCK;
+    if ((int)threadIdx.x < bhead % BLOCK) ++it0;
+    local = it0 < 32 ? __popc(pbits >> it0) : 0;
+  }
+  if (local) atomicAdd(&s_cnt, local);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sum_seg[blockIdx.x] = bhead >= 0 ? start + bhead : -1;
+    sum_peer[blockIdx.x] = s_peer >= 0 ? start + s_peer : -1;
+    sum_cnt[blockIdx.x] = s_cnt;
+  }
+}
+
+// single-block exclusive segmented scan of the chunk aggregates: chunk b
+// receives the aggregate of chunks [0, b)
+__global__ __launch_bounds__(BLOCK) void seg_rank_scan_kernel(
+    const int64_t* __restrict__ sum_seg, const int64_t* __restrict__ sum_peer,
+    const int64_t* __restrict__ sum_cnt, int nblocks,
+    int64_t* __restrict__ car_seg, int64_t* __restrict__ car_peer,
+    int64_t* __restrict__ car_cnt) {
+  __shared__ SegAgg tile[BLOCK];
+  SegAgg carry;  // same value in every thread
+  carry.seg = -1;
+  carry.peer = -1;
+  carry.cnt = 0;
+  for (int t0 = 0; t0 < nblocks; t0 += BLOCK) {
+    int i = t0 + (int)threadIdx.x;
+    SegAgg v;
+    v.seg = -1;
+    v.peer = -1;
+    v.cnt = 0;
+    if (i < nblocks) {
+      v.seg = sum_seg[i];
+      v.peer = sum_peer[i];
+      v.cnt = sum_cnt[i];
+    }
+    tile[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 1; off < BLOCK; off <<= 1) {
+      SegAgg self = tile[threadIdx.x];
+      bool has = (int)threadIdx.x >= off;
+      SegAgg left = self;
+      if (has) left = tile[threadIdx.x - off];
+      __syncthreads();
+      if (has) tile[threadIdx.x] = seg_combine(left, self);
+      __syncthreads();
+    }
+    if (i < nblocks) {
+      SegAgg e = carry;
+      if (threadIdx.x > 0) e = seg_combine(carry, tile[threadIdx.x - 1]);
+      car_seg[i] = e.seg;
+      car_peer[i] = e.peer;
+      car_cnt[i] = e.cnt;
+    }
+    carry = seg_combine(carry, tile[BLOCK - 1]);
+    __syncthreads();
+  }
+}
+
+// window mode: kind 0 row_number, 1 rank, 2 dense_rank
+__global__ __launch_bounds__(BLOCK) void seg_rank_apply_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    SegCols oc, int ncols, int64_t n, const int64_t* __restrict__ car_seg,
+    const int64_t* __restrict__ car_peer, const int64_t* __restrict__ car_cnt,
+    int kind, int64_t* __restrict__ out) {
+  __shared__ SegAgg ws[2][SEG_WAVES];
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  int wave = threadIdx.x / WAVE;
+  SegAgg carry;
+  carry.seg = car_seg[blockIdx.x];
+  carry.peer = car_peer[blockIdx.x];
+  carry.cnt = car_cnt[blockIdx.x];
+  for (int it = 0; it < SEG_ITERS; ++it) {
+    int64_t i0 = start + (int64_t)it * BLOCK;
+    if (i0 >= n) break;  // block-uniform
+    int64_t i = i0 + threadIdx.x;
+    int64_t j;
+    bool h, p;
+    seg_flags(perm, pkeys, oc, ncols, i, n, lane, j, h, p);
+    SegAgg r = seg_block_step(h, p, i0, lane, wave, carry, ws[it & 1]);
+    if (i < n) {
+      int64_t v = kind == 0 ? i - r.seg + 1
+                            : (kind == 1 ? r.peer - r.seg + 1 : r.cnt);
+      out[j] = v;
+    }
+  }
+}
+
+// take mode, pass 1: kept rows per chunk
+__global__ __launch_bounds__(BLOCK) void seg_take_count_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    SegCols oc, int64_t n, const int64_t* __restrict__ car_seg,
+    int64_t n_take, int64_t* __restrict__ bcounts) {
+  __shared__ SegAgg ws[2][SEG_WAVES];
+  __shared__ int lcount;
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  int wave = threadIdx.x / WAVE;
+  if (threadIdx.x == 0) lcount = 0;
+  SegAgg carry;
+  carry.seg = car_seg[blockIdx.x];
+  carry.peer = -1;
+  carry.cnt = 0;
+  int local = 0;
+  for (int it = 0; it < SEG_ITERS; ++it) {
+    int64_t i0 = start + (int64_t)it * BLOCK;
+    if (i0 >= n) break;  // block-uniform
+    int64_t i = i0 + threadIdx.x;
+    int64_t j;
+    bool h, p;
+    seg_flags(perm, pkeys, oc, 0, i, n, lane, j, h, p);
+    SegAgg r = seg_block_step(h, p, i0, lane, wave, carry, ws[it & 1]);
+    if (i < n && i - r.seg < n_take) ++local;
+  }
+  __syncthreads();
+  if (local) atomicAdd(&lcount, local);
+  __syncthreads();
+  if (threadIdx.x == 0) bcounts[blockIdx.x] = lcount;
+}
+
+// take mode, pass 2: emit kept perm values in sorted order
+__global__ __launch_bounds__(BLOCK) void seg_take_emit_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    SegCols oc, int64_t n, const int64_t* __restrict__ car_seg,
+    int64_t n_take, const int64_t* __restrict__ bases, int64_t cap,
+    int64_t* __restrict__ out) {
+  __shared__ SegAgg ws[2][SEG_WAVES];
+  __shared__ int wkeep[2][SEG_WAVES];
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  int wave = threadIdx.x / WAVE;
+  SegAgg carry;
+  carry.seg = car_seg[blockIdx.x];
+  carry.peer = -1;
+  carry.cnt = 0;
+  int64_t base = bases[blockIdx.x];  // same value in every thread
+  for (int it = 0; it < SEG_ITERS; ++it) {
+    int64_t i0 = start + (int64_t)it * BLOCK;
+    if (i0 >= n) break;  // block-uniform
+    int64_t i = i0 + threadIdx.x;
+    int64_t j;
+    bool h, p;
+    seg_flags(perm, pkeys, oc, 0, i, n, lane, j, h, p);
+    SegAgg r = seg_block_step(h, p, i0, lane, wave, carry, ws[it & 1]);
+    bool keep = i < n && i - r.seg < n_take;
+    uint64_t mask = __ballot(keep);
+    int rank = __popcll(mask & ((1ULL << lane) - 1ULL));
+    if (lane == 0) wkeep[it & 1][wave] = __popcll(mask);
+    __syncthreads();
+    int64_t pos = base;
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < SEG_WAVES; ++w) {
+      int c = wkeep[it & 1][w];
+      if (w < wave) pos += c;
+      tot += c;
+    }
+    base += tot;
+    pos += rank;
+    if (keep && pos < cap) out[pos] = j;
+  }
+}
+
+extern "C" {
+
+static SegCols seg_make_cols(const int64_t* const* col_data,
+                             const uint8_t* const* col_valid,
+                             const int* col_is_float, int ncols) {
+  SegCols oc;
+  memset(&oc, 0, sizeof(oc));
+  for (int c = 0; c < ncols; ++c) {
+    oc.data[c] = col_data[c];
+    oc.valid[c] = col_valid[c];
+    oc.is_float[c] = col_is_float[c];
+  }
+  return oc;
+}
+
+// work: 6 * nblocks int64 (chunk aggregates, then chunk carries)
+void launch_seg_rank(const int64_t* perm, const int64_t* pkeys,
+                     const int64_t* const* col_data,
+                     const uint8_t* const* col_valid, const int* col_is_float,
+                     int ncols, int64_t n, int kind, int64_t* work,
+                     int64_t* out, hipStream_t stream) {
+  if (n <= 0) return;
+  int nblocks = (int)((n + SEG_CHUNK - 1) / SEG_CHUNK);
+  SegCols oc = seg_make_cols(col_data, col_valid, col_is_float, ncols);
+  int64_t* w = work;
+  hipLaunchKernelGGL(seg_rank_summary_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, oc, ncols, n, w, w + nblocks,
+                     w + 2 * (int64_t)nblocks);
+  hipLaunchKernelGGL(seg_rank_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, w,
+                     w + nblocks, w + 2 * (int64_t)nblocks, nblocks,
+                     w + 3 * (int64_t)nblocks, w + 4 * (int64_t)nblocks,
+                     w + 5 * (int64_t)nblocks);
+  hipLaunchKernelGGL(seg_rank_apply_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, oc, ncols, n,
+                     w + 3 * (int64_t)nblocks, w + 4 * (int64_t)nblocks,
+                     w + 5 * (int64_t)nblocks, kind, out);
+}
+
+// work: 6 * nblocks int64; bcounts: nblocks; bases: nblocks + 1 (total in
+// bases[nblocks]); out: capacity n
+void launch_seg_take(const int64_t* perm, const int64_t* pkeys, int64_t n,
+                     int64_t n_take, int64_t* work, int64_t* bcounts,
+                     int64_t* bases, int64_t* out, hipStream_t stream) {
+  if (n <= 0) return;
+  int nblocks = (int)((n + SEG_CHUNK - 1) / SEG_CHUNK);
+  SegCols oc;
+  memset(&oc, 0, sizeof(oc));
+  int64_t* w = work;
+  hipLaunchKernelGGL(seg_rank_summary_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, oc, 0, n, w, w + nblocks,
+                     w + 2 * (int64_t)nblocks);
+  hipLaunchKernelGGL(seg_rank_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, w,
+                     w + nblocks, w + 2 * (int64_t)nblocks, nblocks,
+                     w + 3 * (int64_t)nblocks, w + 4 * (int64_t)nblocks,
+                     w + 5 * (int64_t)nblocks);
+  hipLaunchKernelGGL(seg_take_count_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, oc, n, w + 3 * (int64_t)nblocks,
+                     n_take, bcounts);
+  hipLaunchKernelGGL(gbc_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, bcounts,
+                     nblocks, bases);
+  hipLaunchKernelGGL(seg_take_emit_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, oc, n, w + 3 * (int64_t)nblocks,
+                     n_take, bases, n, out);
+}
+
+}  // extern "C"

@@ -5,7 +5,7 @@ RCCL/xGMI; ``gloo`` on CPU for tests).  A distributed dataframe is one
 ``HipDataFrame`` shard per rank; shuffles are RCCL all-to-all-v issued as
 grouped P2P over the 7 xGMI links; the relational hot path (hash join,
 group-by aggregation, repartition) runs the hand-written CDNA4 kernels in
-``csrc/relational.hip``.
+``csrc/*.hip``.
 
 Reference parity: this replaces the reference's Spark/Dask/Ray backends
  while implementing the same ``ExecutionEngine`` contract.

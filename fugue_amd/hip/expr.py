@@ -1,7 +1,7 @@
 """Column-expression evaluation on device frames (torch elementwise ops —
 each lowers to a HIP kernel; fusion of the scalar pipeline comes from
 torch's elementwise fuser, while the relational ops use the hand-written
-kernels in ``csrc/relational.hip``)."""
+kernels in ``csrc/*.hip``)."""
 from typing import Any, Dict, List, Optional, Tuple
 
 import pyarrow as pa

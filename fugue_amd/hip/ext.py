@@ -9,6 +9,17 @@ import threading
 from typing import Any, Optional
 
 _BUILD_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_build")
+# csrc/: the bindings plus one .hip file per kernel family; relational.h
+# (launchers, shared limits) and device_common.h are included by them
+_SOURCES = (
+    "bindings.cpp",
+    "hash_partition.hip",
+    "groupby.hip",
+    "groupby_replay.hip",
+    "join.hip",
+    "select.hip",
+    "segmented.hip",
+)
 _LOCK = threading.Lock()
 _EXT: Optional[Any] = None
 _EXT_ERROR: Optional[Exception] = None
@@ -27,10 +38,7 @@ def build_extension(verbose: bool = False) -> Any:
         src_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
         _EXT = load(
             name="fugue_amd_hip",
-            sources=[
-                os.path.join(src_dir, "bindings.cpp"),
-                os.path.join(src_dir, "relational.hip"),
-            ],
+            sources=[os.path.join(src_dir, f) for f in _SOURCES],
             build_directory=_BUILD_DIR,
             extra_cflags=["-O3"],
             extra_cuda_cflags=["-O3"],

@@ -1,7 +1,7 @@
 """Device relational primitives: row hashing, radix partition, group-by
 aggregation, hash join, sort.
 
-These wrap the hand-written CDNA4 kernels (``csrc/relational.hip``) plus
+These wrap the hand-written CDNA4 kernels (``csrc/*.hip``) plus
 rocPRIM-backed torch primitives (sort/cumsum/unique — the "library GEMM"
 equivalents).  Reference call sites being replaced are listed in
 SURVEY.md §2.3.
@@ -21,7 +21,7 @@ from fugue_amd.hip.ext import get_ext
 from fugue_amd.hip.frame import DeviceColumn, HipDataFrame, StringDeviceColumn
 from fugue_amd.schema import Schema
 
-GB_EMPTY = -0x8000000000000000
+GB_EMPTY = -0x8000000000000000  # GB_EMPTY of csrc/relational.h, as int64
 
 AGG_SUM = 0
 AGG_MIN = 1

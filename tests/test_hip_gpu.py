@@ -791,6 +791,28 @@ def test_topk_select_gpu(engine):
                     )
 
 
+def test_topk_select_edges_gpu(engine):
+    """k at both ends of [1, 16] over 200,000 distinct values (more than
+    the 512 x 256 stage-1 threads, so the grid-stride loop iterates):
+    values and indices exactly as torch.sort orders them."""
+    import torch
+
+    from fugue_amd.hip.ext import get_ext
+
+    n = 200_000
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(29))
+    for vt in ((perm - n // 2).cuda(), ((perm - n // 2).double() * 0.5).cuda()):
+        sv, si = torch.sort(vt)  # ascending; distinct values: one order only
+        for largest in (True, False):
+            for k in (1, 16):
+                ov, oi = get_ext().topk_select(vt, k, largest)
+                ev = sv[-k:].flip(0) if largest else sv[:k]
+                ei = si[-k:].flip(0) if largest else si[:k]
+                assert ov.dtype == vt.dtype and oi.dtype == torch.int64
+                assert torch.equal(ov, ev), (vt.dtype, largest, k)
+                assert torch.equal(oi, ei), (vt.dtype, largest, k)
+
+
 def test_take_presort_matches_pandas_gpu(engine):
     """take() with a single presort key goes through the own top-k
     kernel and matches pandas nsmallest/nlargest."""
