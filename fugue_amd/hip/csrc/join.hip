@@ -526,10 +526,13 @@ __global__ __launch_bounds__(BLOCK) void joinoa_probe_kernel(
       for (int j = 0; j < 4; ++j) {
         if (act[j]) {
           int64_t k = table[2 * h[j]];
-          if (k == key[j]) {
-            match[j] = table[2 * h[j] + 1];
+          // empty first: a probe key equal to the sentinel must not
+          // "match" an empty slot (its idx half is uninitialized); a
+          // build-side sentinel has already set flags[1]
+          if (k == JOA_EMPTY) {
             act[j] = false;
-          } else if (k == JOA_EMPTY) {
+          } else if (k == key[j]) {
+            match[j] = table[2 * h[j] + 1];
             act[j] = false;
           } else {
             h[j] = (h[j] + 1) & tmask;

@@ -499,9 +499,16 @@ void launch_eq2_mask(const int64_t* h1, const int64_t* h2, const int64_t* l1,
 // block over the per-block candidates — read the data once.          //
 // ------------------------------------------------------------------ //
 
+// NaN test that folds to false for the integer instantiations
+__device__ __forceinline__ bool tk_nan(int64_t) { return false; }
+__device__ __forceinline__ bool tk_nan(double v) { return v != v; }
+
 template <typename T, bool LARGEST>
 __device__ __forceinline__ bool tk_before(T a, int64_t ia, T b, int64_t ib) {
-  // strict ordering with index tiebreak (deterministic)
+  // strict total order with index tiebreak (deterministic); NaN ranks
+  // after every number in both directions, NaNs tie with each other
+  bool na = tk_nan(a), nb = tk_nan(b);
+  if (na || nb) return na != nb ? nb : ia < ib;
   if (a != b) return LARGEST ? (a > b) : (a < b);
   return ia < ib;
 }

@@ -1495,7 +1495,20 @@ class HipExecutionEngine(ExecutionEngine):
                         raise NotImplementedError("string presort")
                     asc = _presort[keys_l[0]]
                     vals = c.data
-                    if c.valid is not None:
+                    valid = c.valid
+                    own_topk = (
+                        k <= 16
+                        and vals.dtype in (torch.int64, torch.float64)
+                        and vals.is_cuda
+                    )
+                    if vals.is_floating_point() and not (
+                        own_topk and valid is None
+                    ):
+                        # NaN sorts last like a null; only the own
+                        # kernel orders NaN itself (no extra pass then)
+                        nan = torch.isnan(vals)
+                        valid = ~nan if valid is None else valid & ~nan
+                    if valid is not None:
                         if vals.is_floating_point():
                             sentinel: Any = (
                                 float("inf") if asc else float("-inf")
@@ -1504,11 +1517,9 @@ class HipExecutionEngine(ExecutionEngine):
                             info = torch.iinfo(vals.dtype)
                             sentinel = info.max if asc else info.min
                         vals = torch.where(
-                            c.valid, vals, torch.full_like(vals, sentinel)
+                            valid, vals, torch.full_like(vals, sentinel)
                         )
-                    if k <= 16 and vals.dtype in (
-                        torch.int64, torch.float64
-                    ) and vals.is_cuda:
+                    if own_topk:
                         # own 2-pass register/LDS top-k (k<=16): one data
                         # read instead of rocPRIM's merge-sort cascade
                         from fugue_amd.hip.ext import get_ext

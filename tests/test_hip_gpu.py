@@ -813,6 +813,77 @@ def test_topk_select_edges_gpu(engine):
                 assert torch.equal(oi, ei), (vt.dtype, largest, k)
 
 
+def _topk_nan_ref(vals: np.ndarray, k: int, largest: bool) -> np.ndarray:
+    """Indices of the first k rows when numbers come in the requested
+    direction, NaN after every number, and ties (NaN ties included) go
+    to the lower index."""
+    nan = np.isnan(vals)
+    key = np.where(nan, 0.0, -vals if largest else vals)
+    return np.lexsort((np.arange(len(vals)), key, nan))[:k]
+
+
+@pytest.mark.parametrize("n", [37, 5000, 200_000])
+def test_topk_select_nan_gpu(n):
+    """NaN ranks after every number (±inf included) in both directions."""
+    from fugue_amd.hip.ext import get_ext
+
+    rng = np.random.default_rng(n)
+    mixed = rng.integers(-50, 50, n).astype(np.float64)  # many ties
+    mixed[rng.random(n) < 0.3] = np.nan
+    mixed[0] = np.nan  # the first value a thread's list ever sees
+    mixed[1:5] = [np.inf, -np.inf, -0.0, 0.0]
+    crowded = np.full(n, np.nan)  # more NaNs than n - k: some come back
+    crowded[rng.permutation(n)[:7]] = [3.0, -np.inf, 3.0, np.inf, -1.5, 0.0, 8.0]
+    for name, vals in (
+        ("mixed", mixed), ("crowded", crowded), ("all-nan", np.full(n, np.nan)),
+    ):
+        vt = torch.from_numpy(vals).cuda()
+        for largest in (True, False):
+            for k in (1, 10, 16):
+                ov, oi = get_ext().topk_select(vt, k, largest)
+                ei = _topk_nan_ref(vals, k, largest)
+                msg = f"{name} n={n} k={k} largest={largest}"
+                np.testing.assert_array_equal(oi.cpu().numpy(), ei, err_msg=msg)
+                got = ov.cpu().numpy()
+                np.testing.assert_array_equal(got, vals[ei], err_msg=msg)
+                np.testing.assert_array_equal(
+                    np.signbit(got), np.signbit(vals[ei]), err_msg=msg
+                )
+
+
+@pytest.mark.parametrize("k", [3, 17])
+def test_take_presort_nan_last_gpu(engine, k):
+    """take() puts NaN last in both directions, for k within the own
+    top-k kernel (3) and past it (17), whether the NaNs arrive as nulls
+    from the host or are computed on the device (validity None)."""
+    rng = np.random.default_rng(53)
+    n = 50_000
+    x = rng.random(n)
+    m = np.where(rng.random(n) < 0.01, 0.0, 1.0)
+    m[[0, n - 1]] = 0.0
+    b = np.where(m == 0.0, np.nan, x)
+    pdf = pd.DataFrame(dict(a=np.arange(n), b=b))
+    dev = fa.assign(
+        engine.to_df(pd.DataFrame(dict(a=np.arange(n), x=x, m=m))),
+        b=col("x") * (col("m") / col("m")),  # 0.0 / 0.0 where m is 0
+        engine=engine, as_fugue=True,
+    )
+    assert isinstance(dev, HipDataFrame) and dev.col("b").valid is None
+    assert bool(torch.isnan(dev.col("b").data).any().item())
+    dev = dev[["a", "b"]]
+    for asc in (False, True):
+        exp = pdf.sort_values(
+            "b", ascending=asc, na_position="last", kind="stable"
+        ).head(k).reset_index(drop=True)
+        assert not exp.b.isna().any()
+        presort = "b asc" if asc else "b desc"
+        for src in (pdf, dev):
+            res = fa.take(src, k, presort=presort, engine=engine, as_fugue=True)
+            pd.testing.assert_frame_equal(
+                res.as_pandas().reset_index(drop=True), exp, check_dtype=False
+            )
+
+
 def test_take_presort_matches_pandas_gpu(engine):
     """take() with a single presort key goes through the own top-k
     kernel and matches pandas nsmallest/nlargest."""
