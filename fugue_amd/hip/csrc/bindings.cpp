@@ -187,6 +187,11 @@ std::vector<at::Tensor> gb_aggregate_partitioned(
   // spill format (narrow keys done by the caller)
   record_layout = record_layout && n_aggs == 1 && n < (int64_t(1) << 31);
   if (record_layout || force_simple) staged = false;
+  // the simple per-partition kernel holds its aggregates in a fixed
+  // [GB_LDS_MAX_AGGS x 1024] LDS array
+  TORCH_CHECK(staged || n_aggs <= GB_LDS_MAX_AGGS,
+              "the partitioned group-by takes at most ", GB_LDS_MAX_AGGS,
+              " aggregates per call, got ", n_aggs);
   // narrow < 0 = speculative: run the int32 path with an in-kernel
   // overflow flag; the CALLER checks the returned flag at its existing
   // sync point and re-runs wide if set (no mid-pipeline sync here)
@@ -1142,6 +1147,10 @@ std::vector<at::Tensor> seg_take(at::Tensor perm, at::Tensor pkeys,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  // limits the python layer plans by (ops.py keeps copies for hosts
+  // without the extension; a GPU test compares them)
+  m.attr("PACK_MAX_COLS") = (int64_t)PACK_MAX_COLS;
+  m.attr("GB_LDS_MAX_AGGS") = (int64_t)GB_LDS_MAX_AGGS;
   m.def("hash_column", &hash_column,
         "combine a column into the running row hash");
   m.def("bucket_of", &bucket_of, "hash -> bucket id");

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_lds_kernel(
     int64_t* __restrict__ gcount,
     int64_t tsize) {
   __shared__ int64_t lkeys[LDS_SLOTS];
-  __shared__ double laggs[4 * LDS_SLOTS];
+  __shared__ double laggs[GB_LDS_MAX_AGGS * LDS_SLOTS];
   __shared__ long long lcount[LDS_SLOTS];
   for (int i = threadIdx.x; i < LDS_SLOTS; i += blockDim.x) {
     lkeys[i] = GB_EMPTY;
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(BLOCK) void gb_aggregate_part_kernel(
     int64_t* __restrict__ gcount,
     int64_t tsize) {
   __shared__ int64_t lkeys[LDS_SLOTS];
-  __shared__ double laggs[4 * LDS_SLOTS];
+  __shared__ double laggs[GB_LDS_MAX_AGGS * LDS_SLOTS];
   __shared__ long long lcount[LDS_SLOTS];
   for (int64_t p = blockIdx.x; p < num_parts; p += gridDim.x) {
     for (int i = threadIdx.x; i < LDS_SLOTS; i += blockDim.x) {
@@ -787,7 +787,7 @@ void launch_gb_aggregate(const int64_t* keys, const double* vals,
                          int64_t n, int64_t* tkeys, double* gaggs,
                          int64_t* gcount, int64_t tsize, int use_lds,
                          hipStream_t stream) {
-  if (use_lds && n_aggs <= 4) {
+  if (use_lds && n_aggs <= GB_LDS_MAX_AGGS) {
     hipLaunchKernelGGL(gb_aggregate_lds_kernel, dim3(grid_for(n, 4)),
                        dim3(BLOCK), 0, stream, keys, vals, valids, ops, n_aggs,
                        n, tkeys, gaggs, gcount, tsize);

@@ -11,8 +11,16 @@
 
 #define BLOCK 256  // threads per block, every kernel
 
-// empty-slot key of the group-by hash tables
+// empty-slot key of the group-by hash tables.  Kernel contract: no key
+// handed to a group-by kernel equals GB_EMPTY (a probe would take the
+// first empty slot for a match without claiming it, and the table
+// compaction drops the slot).  ops.groupby_aggregate aggregates such
+// rows apart with the keyless reduction and appends the group.
 #define GB_EMPTY 0x8000000000000000LL
+// most SUM/COUNT aggregates of the LDS pre-aggregating group-by kernels
+// (gb_aggregate_lds_kernel, gb_aggregate_part_kernel): laggs is
+// [GB_LDS_MAX_AGGS x LDS_SLOTS]
+#define GB_LDS_MAX_AGGS 4
 // partitioned group-by: most hash partitions (LDS histogram size)
 #define PART_MAX 4096
 // dense replay: most distinct keys per partition the id table accepts

@@ -890,9 +890,7 @@ class HipExecutionEngine(ExecutionEngine):
             lo = min(self._global_min(c1), self._global_min(c2))
             hi = max(self._global_max(c1), self._global_max(c2))
             mins.append(lo)
-            widths.append(
-                max(1, int(np.ceil(np.log2(max(2, hi - lo + 2)))))
-            )
+            widths.append(dops._code_width(lo, hi))
         if sum(widths) > 63:
             raise NotImplementedError("join key range too wide to pack")
         k1, _ = dops.pack_keys(cols1, mins=mins, widths=widths)
@@ -1984,9 +1982,7 @@ class HipExecutionEngine(ExecutionEngine):
                     lo = self._global_min(kc)
                     hi = self._global_max(kc)
                     pack_mins.append(lo)
-                    pack_widths.append(
-                        max(1, int(np.ceil(np.log2(max(2, hi - lo + 2)))))
-                    )
+                    pack_widths.append(dops._code_width(lo, hi))
                 if sum(pack_widths) > 63:
                     # not packable: co-shuffle rows, then exact local
                     # hashed aggregation (globally exact)

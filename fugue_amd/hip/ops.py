@@ -22,6 +22,11 @@ from fugue_amd.hip.frame import DeviceColumn, HipDataFrame, StringDeviceColumn
 from fugue_amd.schema import Schema
 
 GB_EMPTY = -0x8000000000000000  # GB_EMPTY of csrc/relational.h, as int64
+# copies of two csrc/relational.h limits, for hosts without the extension;
+# the extension exports its own values under the same names, and
+# tests/test_groupby_kernels_gpu.py holds the copies to them
+PACK_MAX_COLS = 8
+GB_LDS_MAX_AGGS = 4
 
 AGG_SUM = 0
 AGG_MIN = 1
@@ -83,8 +88,14 @@ def _hash_rows_cpu(
             import pandas as pd
 
             strings = c.to_arrow().to_pandas()
+            # null cells get null_h below; their placeholder must not hold
+            # a NUL (pandas' object hashing stops at it, and a "\0..."
+            # placeholder changed the hash of "" in the same column).
+            # Known limit of this host twin: for the same reason strings
+            # that differ only after an embedded NUL ("ab", "ab\0") share
+            # one hash here, while the kernel tells them apart (STATUS.md)
             v = pd.util.hash_array(
-                strings.fillna("\0__null__").to_numpy(dtype=object)
+                strings.fillna("").to_numpy(dtype=object)
             ).astype(np.uint64)
             v = _np_mix64(v)
             if c.valid is not None:
@@ -93,6 +104,10 @@ def _hash_rows_cpu(
             raw = c.data.numpy()
             if raw.dtype == np.bool_:
                 raw = raw.astype(np.uint8)
+            elif raw.dtype == np.int16:
+                # hash_rows widens int16 to int32 (sign-extending) before
+                # the kernel hashes the 32 raw bits
+                raw = raw.astype(np.int32)
             bits = raw.view(_unsigned_view_dtype(raw.dtype)).astype(np.uint64)
             v = _np_mix64(bits)
             if c.valid is not None:
@@ -557,10 +572,18 @@ def _compact_groups(
     )
 
 
+def _code_width(lo: int, hi: int) -> int:
+    """Bits of one packed key column: codes run 0 (NULL) .. hi - lo + 1.
+    Exact in Python ints (a float log2 rounds 2**k + 1 down to k bits once
+    k passes 53, and has no value beyond 64 bits)."""
+    return max(1, (int(hi) - int(lo) + 1).bit_length())
+
+
 def _device_packable(key_cols: "Sequence[DeviceColumn]") -> bool:
     # integer dtypes only: the kernels load raw values by width, while
-    # float keys go through the torch path's value-cast to int64
-    return all(
+    # float keys go through the torch path's value-cast to int64; the
+    # kernels take at most PACK_MAX_COLS columns per launch
+    return len(key_cols) <= PACK_MAX_COLS and all(
         (not isinstance(c, StringDeviceColumn))
         and c.data.is_cuda
         and c.data.dtype in (torch.int64, torch.int32, torch.int16)
@@ -601,8 +624,7 @@ def pack_keys(
         if mins is None:
             comp_mins, comp_maxs, est = _key_stats_device(kd, kv, True)
             comp_widths = [
-                max(1, int(np.ceil(np.log2(max(2, hi - lo + 2)))))
-                for lo, hi in zip(comp_mins, comp_maxs)
+                _code_width(lo, hi) for lo, hi in zip(comp_mins, comp_maxs)
             ]
         else:
             comp_mins = list(mins)
@@ -630,6 +652,18 @@ def pack_keys(
     comp_widths = []
     for i, c in enumerate(key_cols):
         d = c.data.to(torch.int64)
+        if mins is None and c.data.is_floating_point() and d.numel() > 0:
+            # the value cast is exact for integral floats only (both zeros
+            # are 0); anything else would merge with its truncation, so
+            # the caller takes its exact host path.  Single-rank only:
+            # with rank-consistent ``mins`` (distributed partial merge) a
+            # rank must not leave the collective plan on its own data, so
+            # non-integral float keys are still truncated there (STATUS.md)
+            exact = (d.to(c.data.dtype) == c.data) & (c.data.abs() < 2.0**62)
+            if c.valid is not None:
+                exact = exact | ~c.valid
+            if not bool(exact.all().item()):
+                raise NotImplementedError("non-integral float group keys")
         if mins is None:
             lo = int(d.min().item()) if d.numel() > 0 else 0
             hi = int(d.max().item()) if d.numel() > 0 else 0
@@ -641,7 +675,7 @@ def pack_keys(
         datas.append(code)
         comp_mins.append(lo)
         if widths is None:
-            w = max(1, int(np.ceil(np.log2(max(2, hi - lo + 2)))))
+            w = _code_width(lo, hi)
             comp_widths.append(w)
         else:
             comp_widths.append(widths[i])
@@ -769,6 +803,46 @@ def _agg_inputs(
     return vals, valids, ops, False
 
 
+def _groupby_with_empty_key(
+    df: HipDataFrame,
+    keys: List[str],
+    aggs: List[Tuple[str, int, str]],
+    packed: "torch.Tensor",
+    expected_groups: int,
+) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor, None]:
+    """``groupby_aggregate`` over a raw int64 key column that holds
+    GB_EMPTY: the rows of that key are one group, reduced by the keyless
+    kernel and appended to the hash aggregation of all other rows (which
+    then meets the kernels' contract).  Off the hot path: it gathers both
+    row sets."""
+    device = packed.device
+    is_empty_key = packed == GB_EMPTY
+    rows = is_empty_key.nonzero(as_tuple=True)[0]
+    rest = (~is_empty_key).nonzero(as_tuple=True)[0]
+    vals, _ = global_aggregate(df.gather_rows(rows), aggs)
+    if rest.numel() > 0:
+        out_keys, out_aggs, out_count, _ = groupby_aggregate(
+            df.gather_rows(rest), keys, aggs, expected_groups=expected_groups
+        )
+    else:
+        out_keys = torch.empty(0, dtype=torch.int64, device=device)
+        out_count = torch.empty(0, dtype=torch.int64, device=device)
+        out_aggs = {
+            oname: torch.empty(0, dtype=torch.float64, device=device)
+            for _, _, oname in aggs
+        }
+    one = lambda v, dt: torch.tensor([v], dtype=dt, device=device)  # noqa: E731
+    return (
+        torch.cat([out_keys, one(GB_EMPTY, torch.int64)]),
+        {
+            oname: torch.cat([out_aggs[oname], one(vals[oname], torch.float64)])
+            for _, _, oname in aggs
+        },
+        torch.cat([out_count, one(int(rows.numel()), torch.int64)]),
+        None,
+    )
+
+
 def groupby_aggregate(
     df: HipDataFrame,
     keys: List[str],
@@ -792,6 +866,23 @@ def groupby_aggregate(
         return _groupby_aggregate_cpu(packed, aggs, df, meta)
     ext = get_ext()
     key_range = None
+    key_stats = None
+    if meta is None and n > 0:
+        # raw int64 keys are the only ones that can equal GB_EMPTY (packed
+        # and re-encoded keys are >= 0); the kernels' contract excludes it
+        # (csrc/relational.h), and the minimum of the memoized key stats
+        # is the presence test.  Without ``expected_groups`` (every engine
+        # call) this is the readback the sizing needs anyway; a caller
+        # that passes ``expected_groups`` now pays one stats launch set
+        # and host sync per key tensor (memoized).  ``key_range`` stays
+        # unset for such callers on purpose: they keep the speculative
+        # int32 narrowing, which tests/test_gb_staged_gpu.py reaches
+        # exactly this way
+        key_stats = _key_stats_device([packed], [None], True)
+        if key_stats[0][0] == GB_EMPTY:
+            return _groupby_with_empty_key(
+                df, keys, aggs, packed, expected_groups or key_stats[2]
+            )
     if expected_groups is None:
         # sample-based distinct-count estimate (Chao83: D ≈ d + f1²/(2·f2),
         # robust when the sample is mostly singletons — a linear scale-up
@@ -799,10 +890,8 @@ def groupby_aggregate(
         # single host readback; for meta-None keys the same readback
         # carries min/max so the int32-narrowing decision needs no
         # speculative overflow check.
-        if meta is None and n > 0:
-            key_lo, key_hi, expected_groups = _key_stats_device(
-                [packed], [None], True
-            )
+        if key_stats is not None:
+            key_lo, key_hi, expected_groups = key_stats
             key_range = (key_lo[0], key_hi[0])
         elif n > 0:
             expected_groups = (meta or {}).get("est")
@@ -813,7 +902,16 @@ def groupby_aggregate(
         else:
             expected_groups = 1
     sum_count_only = all(op in (AGG_SUM, AGG_COUNT) for _, op, _ in aggs)
-    if not (expected_groups > 100_000 and valids is None and sum_count_only):
+    # the partitioned path aggregates in a per-partition LDS table that
+    # holds at most GB_LDS_MAX_AGGS aggregates; wider calls go to the HBM
+    # table, like every other shape that path does not take
+    partitioned = (
+        expected_groups > 100_000
+        and valids is None
+        and sum_count_only
+        and vals.shape[0] <= GB_LDS_MAX_AGGS
+    )
+    if not partitioned:
         use_lds = expected_groups <= 100_000 and sum_count_only
         tkeys, gaggs, gcount = ext.gb_aggregate(
             keys=packed, vals=vals, valids=valids, ops=ops,

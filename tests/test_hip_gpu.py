@@ -899,13 +899,33 @@ def test_take_presort_matches_pandas_gpu(engine):
 def test_float_group_keys_gpu(engine):
     """Float group keys take the value-cast path, not the raw-bits pack
     (regression: r02f test_select conformance failure)."""
-    pdf = pd.DataFrame(dict(a=[1.0, 1.0, 3.0, None, None], b=[1, 1, 4, 3, 4]))
+    pdf = pd.DataFrame(
+        dict(a=[1.0, 1.0, 3.0, None, None, 0.0, -0.0], b=[1, 1, 4, 3, 4, 5, 6])
+    )
     res = fa.select(
         pdf, col("a"), f.sum(col("b")).cast(float).alias("b"),
         engine=engine, as_fugue=True,
     )
     got = sorted(res.as_array(), key=lambda r: (r[0] is None, r[0]))
-    assert got == [[1.0, 2.0], [3.0, 4.0], [None, 7.0]]
+    # both zeros are one group
+    assert got == [[0.0, 11.0], [1.0, 2.0], [3.0, 4.0], [None, 7.0]]
+
+
+def test_fractional_float_group_keys_gpu(engine):
+    """Float keys with a fractional part, an infinity or a NaN do not
+    survive the value cast; they must not merge with their truncation."""
+    pdf = pd.DataFrame(
+        dict(a=[1.0, 1.5, 1.5, -0.5, 0.0, 0.25, np.inf], b=[1, 2, 3, 4, 5, 6, 7])
+    )
+    res = fa.select(
+        pdf, col("a"), f.sum(col("b")).cast(float).alias("b"),
+        engine=engine, as_fugue=True,
+    )
+    got = sorted(res.as_array(), key=lambda r: r[0])
+    assert got == [
+        [-0.5, 4.0], [0.0, 5.0], [0.25, 6.0], [1.0, 1.0], [1.5, 5.0],
+        [np.inf, 7.0],
+    ]
 
 
 def test_open_addressed_join_gpu(engine, monkeypatch):
