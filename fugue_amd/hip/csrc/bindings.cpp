@@ -458,6 +458,140 @@ at::Tensor gb_replay_dense(at::Tensor vals, at::Tensor gid,
   return out_sum;
 }
 
+// ---- binned dense replay: values laid out by bins of M partitions ----
+
+namespace {
+// bin arrays are int64 [B+1] on the GPU; returns B
+int64_t check_bins(const at::Tensor& bin_offsets) {
+  check_gpu(bin_offsets, "bin_offsets");
+  TORCH_CHECK(bin_offsets.scalar_type() == at::kLong &&
+                  bin_offsets.dim() == 1 && bin_offsets.numel() >= 2 &&
+                  bin_offsets.numel() - 1 <= BIN_MAX,
+              "bin_offsets must be int64 [B+1], B <= ", BIN_MAX);
+  return bin_offsets.numel() - 1;
+}
+
+void dense_aggregate_binned_into(const at::Tensor& gid,
+                                 const at::Tensor& pvals,
+                                 const at::Tensor& bin_offsets,
+                                 const at::Tensor& bin_group_base,
+                                 const at::Tensor& bin_chunk_base,
+                                 int64_t total_chunks, int64_t chunk,
+                                 int64_t slots, at::Tensor& out_sum) {
+  check_gpu(gid, "gid");
+  check_gpu(pvals, "pvals");
+  int64_t nbins = check_bins(bin_offsets);
+  check_gpu(bin_group_base, "bin_group_base");
+  check_gpu(bin_chunk_base, "bin_chunk_base");
+  check_dense_slots(slots);
+  int64_t n = gid.numel();
+  TORCH_CHECK(gid.scalar_type() == at::kInt, "gid must be int32");
+  TORCH_CHECK(pvals.scalar_type() == at::kDouble && pvals.numel() == n,
+              "pvals must be fp64 [n]");
+  TORCH_CHECK(bin_group_base.scalar_type() == at::kLong &&
+                  bin_chunk_base.scalar_type() == at::kLong &&
+                  bin_group_base.numel() == nbins + 1 &&
+                  bin_chunk_base.numel() == nbins + 1,
+              "bin_group_base/bin_chunk_base must be int64 [B+1]");
+  TORCH_CHECK(chunk >= 1, "chunk must be >= 1");
+  TORCH_CHECK(total_chunks >= 0, "total_chunks must be >= 0");
+  if (n > 0 && total_chunks > 0) {
+    launch_gb_dense_aggregate_binned(
+        gid.data_ptr<int32_t>(), pvals.data_ptr<double>(), n,
+        bin_offsets.data_ptr<int64_t>(), bin_group_base.data_ptr<int64_t>(),
+        bin_chunk_base.data_ptr<int64_t>(), (int)nbins, total_chunks,
+        out_sum.numel(), out_sum.data_ptr<double>(), chunk, (int)slots,
+        current_stream());
+  }
+}
+}  // namespace
+
+// Preparation of the tile-coalesced scatter into the binned layout.  pos
+// is every row's recorded position, gid the dense ids by recorded
+// position, bin_offsets [B+1] the first recorded position of every bin.
+// A row goes to bin_offsets[b] + (rows of bin b in earlier tiles) + (its
+// rank among the bin-b rows of its own tile, by recorded position), so
+// every (tile, bin) is one contiguous run and the runs of consecutive
+// tiles are adjacent.  Returns (rank, dst, gid in the new order).
+std::vector<at::Tensor> scatter_tile_prepare_binned(at::Tensor pos,
+                                                    at::Tensor gid,
+                                                    at::Tensor bin_offsets,
+                                                    int64_t tile) {
+  check_gpu(pos, "pos");
+  check_gpu(gid, "gid");
+  TORCH_CHECK(pos.scalar_type() == at::kInt, "pos must be int32");
+  int64_t n = pos.numel();
+  TORCH_CHECK(gid.scalar_type() == at::kInt && gid.numel() == n,
+              "gid must be int32 [n]");
+  check_tile(tile);
+  int64_t nbins = check_bins(bin_offsets);
+  auto rank = at::empty({n}, pos.options().dtype(at::kShort));
+  auto dst = at::empty({n}, pos.options());
+  auto gid_new = at::empty({n}, pos.options());
+  if (n == 0) return {rank, dst, gid_new};
+  auto stream = current_stream();
+  int64_t ntiles = (n + tile - 1) / tile;
+  auto counts = at::empty({ntiles, nbins}, pos.options());
+  launch_scatter_bin_count(pos.data_ptr<int32_t>(), n, (int)tile,
+                           bin_offsets.data_ptr<int64_t>(), (int)nbins,
+                           counts.data_ptr<int32_t>(), stream);
+  // run_delta[t][b] = bin_offsets[b] + rows of bin b in tiles before t
+  //                   - rows of tile t in bins before b
+  auto run_delta = (bin_offsets.slice(0, 0, nbins).unsqueeze(0) +
+                    (counts.cumsum(0, at::kLong) - counts) -
+                    (counts.cumsum(1, at::kLong) - counts))
+                       .contiguous();
+  launch_scatter_tile_prep_binned(
+      pos.data_ptr<int32_t>(), n, (int)tile, bin_offsets.data_ptr<int64_t>(),
+      (int)nbins, run_delta.data_ptr<int64_t>(), gid.data_ptr<int32_t>(),
+      (uint16_t*)rank.data_ptr<int16_t>(), dst.data_ptr<int32_t>(),
+      gid_new.data_ptr<int32_t>(), stream);
+  return {rank, dst, gid_new};
+}
+
+// out_sum[g] = sum of pvals[j] over gid[j] == g for rows laid out by
+// bins.  bin_group_base [B+1] is the first id of every bin,
+// bin_chunk_base [B+1] the prefix of ceil(rows_b / chunk) and
+// total_chunks its last entry.
+at::Tensor gb_dense_aggregate_binned(at::Tensor gid, at::Tensor pvals,
+                                     at::Tensor bin_offsets,
+                                     at::Tensor bin_group_base,
+                                     at::Tensor bin_chunk_base,
+                                     int64_t total_chunks, int64_t n_groups,
+                                     int64_t chunk, int64_t slots) {
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  auto out_sum = at::zeros({n_groups}, pvals.options());
+  dense_aggregate_binned_into(gid, pvals, bin_offsets, bin_group_base,
+                              bin_chunk_base, total_chunks, chunk, slots,
+                              out_sum);
+  return out_sum;
+}
+
+// One replayed step over the binned layout: the tile scatter with the
+// binned (rank, dst), then the bin-aligned aggregate.
+at::Tensor gb_replay_binned(at::Tensor vals, at::Tensor gid, at::Tensor rank,
+                            at::Tensor dst, at::Tensor bin_offsets,
+                            at::Tensor bin_group_base,
+                            at::Tensor bin_chunk_base, int64_t total_chunks,
+                            int64_t n_groups, int64_t chunk, int64_t slots,
+                            int64_t tile) {
+  check_gpu(vals, "vals");
+  int64_t n = gid.numel();
+  TORCH_CHECK(vals.scalar_type() == at::kDouble && vals.numel() == n,
+              "vals must be fp64 [1, n]");
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  TORCH_CHECK(dst.numel() == n, "dst must be int32 [n]");
+  auto pvals = at::empty({n}, vals.options());
+  scatter_tile_into(vals.view({n}), rank, dst, tile, pvals);
+  auto out_sum = at::zeros({n_groups}, vals.options());
+  dense_aggregate_binned_into(gid, pvals, bin_offsets, bin_group_base,
+                              bin_chunk_base, total_chunks, chunk, slots,
+                              out_sum);
+  return out_sum;
+}
+
 std::vector<at::Tensor> join_build(at::Tensor keys, int64_t tsize) {
   check_gpu(keys, "keys");
   TORCH_CHECK((tsize & (tsize - 1)) == 0, "tsize must be a power of 2");
@@ -1192,7 +1326,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_groups"), py::arg("chunk"), py::arg("slots"),
         py::arg("tile") = 0, py::arg("rank") = py::none(),
         py::arg("dst") = py::none(), py::arg("pos") = py::none());
-  m.def("join_build", &join_build, "build chained hash table");
+  m.def("scatter_tile_prepare_binned", &scatter_tile_prepare_binned,
+        "tile scatter preparation into the binned layout: rank, dst, gid",
+        py::arg("pos"), py::arg("gid"), py::arg("bin_offsets"),
+        py::arg("tile"));
+  m.def("gb_dense_aggregate_binned", &gb_dense_aggregate_binned,
+        "sum per dense group id over the binned layout", py::arg("gid"),
+        py::arg("pvals"), py::arg("bin_offsets"), py::arg("bin_group_base"),
+        py::arg("bin_chunk_base"), py::arg("total_chunks"),
+        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"));
+  m.def("gb_replay_binned", &gb_replay_binned,
+        "replayed step over the binned layout: scatter + aggregate",
+        py::arg("vals"), py::arg("gid"), py::arg("rank"), py::arg("dst"),
+        py::arg("bin_offsets"), py::arg("bin_group_base"),
+        py::arg("bin_chunk_base"), py::arg("total_chunks"),
+        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"),
+        py::arg("tile"));
+  m.def("join_build",&join_build, "build chained hash table");
   m.def("join_emit_unique", &join_emit_unique,
         "single-pass join emit for unique build keys");
   m.def("hash_string_column", &hash_string_column,

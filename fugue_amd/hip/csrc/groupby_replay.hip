@@ -22,7 +22,11 @@
 //    so a replayed step is the tile-coalesced value scatter           //
 //    (scatter_tile_kernel) and one LDS f64 add per row                //
 //    (gb_dense_aggregate_kernel): no keys, hashing, CAS, counting,    //
-//    table fills, compaction or host readback.                        //
+//    table fills, compaction or host readback.  The values are laid   //
+//    out by bins of M consecutive partitions (M chosen on the host so //
+//    a bin's ids fit the LDS table), which makes the scatter's runs M //
+//    times longer (scatter_tile_prep_binned_kernel,                   //
+//    gb_dense_aggregate_binned_kernel); M = 1 is the partition layout.//
 // ------------------------------------------------------------------ //
 
 __global__ __launch_bounds__(BLOCK) void scatter_by_pos_kernel(
@@ -203,6 +207,90 @@ __global__ __launch_bounds__(BLOCK) void scatter_tile_prep_kernel(
   }
 }
 
+// Binned value layout.  The replay does not need the recorded layout's
+// hash partitions, only that the ids of a stretch of rows fit the
+// aggregate's LDS table.  M consecutive partitions form a bin (one
+// contiguous id range); rows are re-placed bin-major, and inside a bin in
+// tile order, so a (tile, bin) run is M times longer than a (tile,
+// partition) run.  bin_offsets is [B+1]: the first recorded position of
+// every bin, i.e. offsets[::M].
+
+// largest b in [0, nb) with bounds[b] <= x, for ascending bounds[0] <= x
+__device__ __forceinline__ int bin_of(const int64_t* __restrict__ bounds,
+                                      int nb, int64_t x) {
+  int lo = 0, hi = nb;
+  while (hi - lo > 1) {
+    int mid = (lo + hi) >> 1;
+    if (bounds[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// counts[tile][b] = rows of the tile whose recorded position is in bin b
+__global__ __launch_bounds__(BLOCK) void scatter_bin_count_kernel(
+    const int32_t* __restrict__ pos, int64_t n, int C,
+    const int64_t* __restrict__ bin_offsets, int nbins,
+    int32_t* __restrict__ counts) {
+  __shared__ int lhist[BIN_MAX];
+  int64_t ntiles = (n + C - 1) / C;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (int b = threadIdx.x; b < nbins; b += blockDim.x) lhist[b] = 0;
+    __syncthreads();
+    int64_t t0 = tile * C;
+    int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+    for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+      int64_t p = (int64_t)(uint32_t)pos[t0 + i];
+      if (p < n) atomicAdd(&lhist[bin_of(bin_offsets, nbins, p)], 1);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nbins; b += blockDim.x)
+      counts[tile * nbins + b] = lhist[b];
+    __syncthreads();
+  }
+}
+
+// scatter_tile_prep_kernel for the binned layout.  The sort by recorded
+// position already groups a tile's rows by bin, so the tile's r-th ranked
+// row goes to run_delta[tile][b] + r, where run_delta[tile][b] =
+// bin_offsets[b] + (rows of bin b in earlier tiles) - (first rank of bin
+// b in this tile), prepared by the caller from the count matrix.  The
+// row's dense id moves with it: gid_new[new] = gid_old[old].  The sort
+// buffer is all of the LDS, so bin_offsets is searched in global memory.
+__global__ __launch_bounds__(BLOCK) void scatter_tile_prep_binned_kernel(
+    const int32_t* __restrict__ pos, int64_t n, int C,
+    const int64_t* __restrict__ bin_offsets, int nbins,
+    const int64_t* __restrict__ run_delta,
+    const int32_t* __restrict__ gid_old, uint16_t* __restrict__ rank,
+    int32_t* __restrict__ dst, int32_t* __restrict__ gid_new) {
+  extern __shared__ unsigned long long tile_sort[];
+  int64_t ntiles = (n + C - 1) / C;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t t0 = tile * C;
+    int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+    for (int i = threadIdx.x; i < C; i += blockDim.x) {
+      tile_sort[i] = i < cnt ? (((unsigned long long)(uint32_t)pos[t0 + i]
+                                 << 16) | (unsigned long long)i)
+                             : ~0ULL;
+    }
+    __syncthreads();
+    lds_bitonic_sort<unsigned long long>(tile_sort, C);
+    for (int r = threadIdx.x; r < cnt; r += blockDim.x) {
+      unsigned long long e = tile_sort[r];
+      int64_t p = (int64_t)(e >> 16);
+      rank[t0 + (int)(e & 0xffffULL)] = (uint16_t)r;
+      // a position outside [0, n) (not a permutation) gets a destination
+      // the scatter's own bound check drops
+      int64_t d = -1;
+      if (p < n) {
+        d = run_delta[tile * nbins + bin_of(bin_offsets, nbins, p)] + r;
+        if ((uint64_t)d < (uint64_t)n) gid_new[d] = gid_old[p]; else d = -1;
+      }
+      dst[t0 + r] = (int32_t)d;
+    }
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------ //
 // dense replay: per-step kernels                                      //
 // ------------------------------------------------------------------ //
@@ -328,6 +416,76 @@ __global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_kernel(
   }
 }
 
+// Dense replay aggregate over the binned layout: block work is a chunk of
+// one bin, never a chunk of the whole row range, so the table base is the
+// bin's first id and a bin no wider than the table adds nothing to global
+// memory before the flush.  Virtual chunk v belongs to the bin b with
+// bin_chunk_base[b] <= v < bin_chunk_base[b + 1] ([B+1], the prefix of
+// ceil(rows_b / chunk)); empty bins own no chunk.  The out-of-table guard
+// of gb_dense_aggregate_kernel stays, so any geometry is exact.  Every
+// thread searches bin_chunk_base itself (block-uniform, B+1 entries):
+// with 8192 slots lsum is the whole 64KB and there is no room for a
+// shared base.
+template <int SLOTS>
+__global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_binned_kernel(
+    const int32_t* __restrict__ gid, const double* __restrict__ part_vals,
+    int64_t n, const int64_t* __restrict__ bin_offsets,
+    const int64_t* __restrict__ bin_group_base,
+    const int64_t* __restrict__ bin_chunk_base, int nbins,
+    int64_t total_chunks, int64_t n_groups, double* __restrict__ out_sum,
+    int64_t chunk) {
+  __shared__ double lsum[SLOTS];
+  for (int64_t vc = blockIdx.x; vc < total_chunks; vc += gridDim.x) {
+    for (int i = threadIdx.x; i < SLOTS; i += blockDim.x) lsum[i] = 0.0;
+    const int b = bin_of(bin_chunk_base, nbins, vc);
+    int64_t start = bin_offsets[b] + (vc - bin_chunk_base[b]) * chunk;
+    int64_t end = start + chunk;
+    const int64_t bin_end = bin_offsets[b + 1];
+    if (end > bin_end) end = bin_end;
+    // rows read stay inside [0, n) whatever the bin arrays hold
+    if (start < 0) start = 0;
+    if (end > n) end = n;
+    const int base = (int)bin_group_base[b];
+    __syncthreads();
+    int64_t i = start + threadIdx.x;
+    const int64_t stride = (int64_t)blockDim.x;
+    for (; i + 3 * stride < end; i += 4 * stride) {
+      int g[4];
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) g[u] = gid[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = part_vals[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        unsigned rel = (unsigned)(g[u] - base);
+        if (rel < (unsigned)SLOTS) {
+          atomicAdd(&lsum[rel], v[u]);
+        } else if ((uint64_t)g[u] < (uint64_t)n_groups) {
+          atomicAdd(&out_sum[g[u]], v[u]);
+        }
+      }
+    }
+    for (; i < end; i += stride) {
+      int g = gid[i];
+      double v = part_vals[i];
+      unsigned rel = (unsigned)(g - base);
+      if (rel < (unsigned)SLOTS) {
+        atomicAdd(&lsum[rel], v);
+      } else if ((uint64_t)g < (uint64_t)n_groups) {
+        atomicAdd(&out_sum[g], v);
+      }
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < SLOTS; s += blockDim.x) {
+      double v = lsum[s];
+      if (v != 0.0 && (int64_t)base + s < n_groups)
+        atomicAdd(&out_sum[(int64_t)base + s], v);
+    }
+    __syncthreads();
+  }
+}
+
 extern "C" {
 
 void launch_gb_dense_count(const int64_t* pkeys, const int64_t* offsets,
@@ -390,6 +548,57 @@ void launch_gb_dense_aggregate(const int32_t* gid, const double* part_vals,
     default:
       hipLaunchKernelGGL((gb_dense_aggregate_kernel<4096>), g, b, 0, stream,
                          gid, part_vals, n, offsets, group_base, num_parts,
+                         n_groups, out_sum, chunk);
+  }
+}
+
+// one-time preparation of the binned layout (nbins <= BIN_MAX)
+void launch_scatter_bin_count(const int32_t* pos, int64_t n, int tile,
+                              const int64_t* bin_offsets, int nbins,
+                              int32_t* counts, hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_bin_count_kernel, dim3(chunk_grid(n, tile)),
+                     dim3(BLOCK), 0, stream, pos, n, tile, bin_offsets, nbins,
+                     counts);
+}
+
+void launch_scatter_tile_prep_binned(const int32_t* pos, int64_t n, int tile,
+                                     const int64_t* bin_offsets, int nbins,
+                                     const int64_t* run_delta,
+                                     const int32_t* gid_old, uint16_t* rank,
+                                     int32_t* dst, int32_t* gid_new,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_tile_prep_binned_kernel,
+                     dim3(chunk_grid(n, tile)), dim3(BLOCK),
+                     (size_t)tile * sizeof(unsigned long long), stream, pos, n,
+                     tile, bin_offsets, nbins, run_delta, gid_old, rank, dst,
+                     gid_new);
+}
+
+// chunk > 0 is the one bin_chunk_base was built with
+void launch_gb_dense_aggregate_binned(
+    const int32_t* gid, const double* part_vals, int64_t n,
+    const int64_t* bin_offsets, const int64_t* bin_group_base,
+    const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
+    int64_t n_groups, double* out_sum, int64_t chunk, int slots,
+    hipStream_t stream) {
+  dim3 g(chunk_grid(total_chunks, 1)), b(BLOCK);
+  switch (slots) {
+    case 2048:
+      hipLaunchKernelGGL((gb_dense_aggregate_binned_kernel<2048>), g, b, 0,
+                         stream, gid, part_vals, n, bin_offsets,
+                         bin_group_base, bin_chunk_base, nbins, total_chunks,
+                         n_groups, out_sum, chunk);
+      break;
+    case 4096:
+      hipLaunchKernelGGL((gb_dense_aggregate_binned_kernel<4096>), g, b, 0,
+                         stream, gid, part_vals, n, bin_offsets,
+                         bin_group_base, bin_chunk_base, nbins, total_chunks,
+                         n_groups, out_sum, chunk);
+      break;
+    default:
+      hipLaunchKernelGGL((gb_dense_aggregate_binned_kernel<8192>), g, b, 0,
+                         stream, gid, part_vals, n, bin_offsets,
+                         bin_group_base, bin_chunk_base, nbins, total_chunks,
                          n_groups, out_sum, chunk);
   }
 }

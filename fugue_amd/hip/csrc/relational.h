@@ -25,6 +25,8 @@
 #define PART_MAX 4096
 // dense replay: most distinct keys per partition the id table accepts
 #define DENSE_ASSIGN_MAX 2048
+// binned dense replay: most bins (LDS histogram of the bin count kernel)
+#define BIN_MAX 4096
 
 // group-by key preparation: most key columns per pack / key-stats launch
 #define PACK_MAX_COLS 8
@@ -156,6 +158,21 @@ void launch_gb_dense_aggregate(const int32_t* gid, const double* part_vals,
                                const int64_t* group_base, int num_parts,
                                int64_t n_groups, double* out_sum,
                                int64_t chunk, int slots, hipStream_t stream);
+void launch_scatter_bin_count(const int32_t* pos, int64_t n, int tile,
+                              const int64_t* bin_offsets, int nbins,
+                              int32_t* counts, hipStream_t stream);
+void launch_scatter_tile_prep_binned(const int32_t* pos, int64_t n, int tile,
+                                     const int64_t* bin_offsets, int nbins,
+                                     const int64_t* run_delta,
+                                     const int32_t* gid_old, uint16_t* rank,
+                                     int32_t* dst, int32_t* gid_new,
+                                     hipStream_t stream);
+void launch_gb_dense_aggregate_binned(
+    const int32_t* gid, const double* part_vals, int64_t n,
+    const int64_t* bin_offsets, const int64_t* bin_group_base,
+    const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
+    int64_t n_groups, double* out_sum, int64_t chunk, int slots,
+    hipStream_t stream);
 
 // ---- join.hip ----
 void launch_join_build(const int64_t* keys, int64_t n, int32_t* heads,

@@ -231,8 +231,9 @@ _KEY_STATS_MEMO_CAP = 128
 # null-free fp64 column, FUGUE_GB_REPLAY_DENSE=1) caches per row the
 # dense group id (4 B) and the tile scatter's rank + destination
 # (2 B + 4 B) = 10 B/row, plus keys and counts per GROUP; pkeys and pos
-# are dropped.  Two entries ~1.25GB each at 125M rows — bound the cache
-# tightly.
+# are dropped (the same 10 B/row when the values are laid out by bins
+# of partitions, FUGUE_GB_REPLAY_BIN_PARTS).  Two entries ~1.25GB each
+# at 125M rows — bound the cache tightly.
 _LAYOUT_MEMO: "Dict[Tuple[Any, ...], Any]" = {}
 _LAYOUT_MEMO_CAP = 2
 # key tensors seen once (candidates): recording uses the slower simple
@@ -323,7 +324,10 @@ class _DenseLayout:
     """Recorded layout replayed through ``gb_replay_dense``: the value
     scatter is either tile-coalesced (``tile`` > 0: ``rank`` and ``dst``
     from ``scatter_tile_prepare``) or by recorded position (``tile`` ==
-    0: ``pos``)."""
+    0: ``pos``).  With ``bin_parts`` > 1 the values are laid out by bins
+    of that many consecutive hash partitions instead (``rank``, ``dst``
+    and ``gid`` from ``scatter_tile_prepare_binned``; ``gid`` is then in
+    binned order) and the bin arrays drive the aggregate."""
 
     ref: Any
     gid: "torch.Tensor"
@@ -337,6 +341,13 @@ class _DenseLayout:
     pos: Optional["torch.Tensor"]
     tile: int
     hits: int = 0  # replayed steps served by this entry
+    bin_parts: int = 1  # partitions per bin (1: the partition layout)
+    bin_offsets: Optional["torch.Tensor"] = None  # [B+1] offsets[::M]
+    bin_group_base: Optional["torch.Tensor"] = None  # [B+1] group_base[::M]
+    bin_chunk_base: Optional["torch.Tensor"] = None  # [B+1] chunk prefix
+    bin_chunks: int = 0  # total aggregate chunks over all bins
+    bin_chunk: int = 0  # rows per aggregate chunk bin_chunk_base is for
+    bin_slots: int = 0  # table slots the bin width was chosen for
 
 
 def _layout_get(lkey: tuple) -> Any:
@@ -351,27 +362,89 @@ def _layout_put(lkey: tuple, ent: Any) -> None:
     _LAYOUT_MEMO[lkey] = ent
 
 
+def _choose_bin_parts(
+    group_base: List[int], num_parts: int, max_parts: int, slots: int
+) -> int:
+    """Partitions per bin: the largest power of two that is at most
+    ``max_parts``, divides ``num_parts`` and keeps every bin's group ids
+    within ``slots`` (``group_base`` is the host copy, [P+1])."""
+    m = 1
+    while (
+        m * 2 <= max_parts
+        and num_parts % (m * 2) == 0
+        and max(
+            group_base[b + m * 2] - group_base[b]
+            for b in range(0, num_parts, m * 2)
+        ) <= slots
+    ):
+        m *= 2
+    return m
+
+
 def _prepare_dense_layout(
     ext: Any, packed: "torch.Tensor", pkeys: "torch.Tensor",
     pos: "torch.Tensor", num_parts: int, tile: int,
+    bin_parts: int = 1, bin_slots: int = 8192, bin_chunk: int = 65536,
 ) -> Optional[_DenseLayout]:
     """One-time preparation of the dense replay layout from the recorded
     partitioned keys (int64) and per-row spill positions; None when it is
     declined (a partition's distinct keys overflow the id-assignment
     table, or G >= 2^31) and the plain replay entry must be kept.  One
-    host readback, once per key tensor."""
+    host readback, once per key tensor.  ``bin_parts`` is the most
+    partitions a bin of the value layout may hold (1: keep the partition
+    layout); the width used is the widest whose bins fit ``bin_slots``."""
     offsets, distinct = ext.gb_dense_count(pkeys=pkeys, num_parts=num_parts)
     group_base = torch.zeros(
         num_parts + 1, dtype=torch.int64, device=pkeys.device
     )
     torch.cumsum(distinct, 0, out=group_base[1:])
-    dmax, n_groups = torch.stack([distinct.max(), group_base[-1]]).tolist()
+    binned = tile > 0 and bin_parts > 1
+    if binned:
+        # the same single readback also carries what the bin width and
+        # the chunk count are chosen from
+        host = torch.cat(
+            [distinct.max().reshape(1), group_base, offsets]
+        ).tolist()
+        dmax, gb_host = host[0], host[1 : num_parts + 2]
+        off_host = host[num_parts + 2 :]
+        n_groups = gb_host[-1]
+    else:
+        dmax, n_groups = torch.stack(
+            [distinct.max(), group_base[-1]]
+        ).tolist()
     if dmax > int(ext.dense_assign_max()) or n_groups >= (1 << 31):
         return None
     gid, out_keys, out_count = ext.gb_dense_assign(
         pkeys=pkeys, offsets=offsets, group_base=group_base,
         n_groups=n_groups,
     )
+    m = 1
+    if binned:
+        m = _choose_bin_parts(gb_host, num_parts, bin_parts, bin_slots)
+    if m > 1:
+        bin_offsets = offsets[::m].contiguous()
+        bin_rows = [
+            off_host[b + m] - off_host[b] for b in range(0, num_parts, m)
+        ]
+        chunks = torch.tensor(
+            [(r + bin_chunk - 1) // bin_chunk for r in bin_rows],
+            dtype=torch.int64,
+        )
+        bin_chunk_base = torch.zeros(chunks.numel() + 1, dtype=torch.int64)
+        torch.cumsum(chunks, 0, out=bin_chunk_base[1:])
+        rank, dst, gid = ext.scatter_tile_prepare_binned(
+            pos=pos, gid=gid, bin_offsets=bin_offsets, tile=tile
+        )
+        return _DenseLayout(
+            ref=weakref.ref(packed), gid=gid, offsets=offsets,
+            group_base=group_base, n_groups=int(n_groups),
+            out_keys=out_keys, out_count=out_count, rank=rank, dst=dst,
+            pos=None, tile=tile, bin_parts=m, bin_offsets=bin_offsets,
+            bin_group_base=group_base[::m].contiguous(),
+            bin_chunk_base=bin_chunk_base.to(pkeys.device),
+            bin_chunks=int(bin_chunk_base[-1]), bin_chunk=bin_chunk,
+            bin_slots=bin_slots,
+        )
     rank = dst = None
     if tile > 0:
         rank, dst = ext.scatter_tile_prepare(pos, tile)
@@ -406,6 +479,16 @@ class _GbKnobs:
     # FUGUE_GB_DENSE_SLOTS: LDS table slots of the dense replay
     # aggregate (2048, 4096 or 8192; 8 B per slot)
     dense_slots: int = 4096
+    # FUGUE_GB_REPLAY_BIN_PARTS: most consecutive hash partitions merged
+    # into one bin of the replayed value layout (a power of two; 1 keeps
+    # the partition layout).  A (tile, bin) scatter run is that many
+    # times longer than a (tile, partition) run.  The width used is the
+    # widest whose bins' group ids fit the binned aggregate's table.
+    replay_bin_parts: int = 8
+    # FUGUE_GB_BIN_SLOTS / FUGUE_GB_BIN_CHUNK: LDS table slots (2048,
+    # 4096 or 8192) and rows per chunk of the binned dense aggregate
+    bin_slots: int = 8192
+    bin_chunk: int = 65536
 
     @classmethod
     def from_env(cls) -> "_GbKnobs":
@@ -418,6 +501,14 @@ class _GbKnobs:
                 "in [512, 8192]"
             )
         slots = int(env("FUGUE_GB_DENSE_SLOTS", "4096"))
+        bin_parts = int(env("FUGUE_GB_REPLAY_BIN_PARTS", "8"))
+        if bin_parts < 1 or bin_parts & (bin_parts - 1):
+            raise ValueError(
+                f"FUGUE_GB_REPLAY_BIN_PARTS={bin_parts}: expected a power "
+                "of two >= 1"
+            )
+        bin_slots = int(env("FUGUE_GB_BIN_SLOTS", "8192"))
+        bin_chunk = int(env("FUGUE_GB_BIN_CHUNK", "65536"))
         return cls(
             staged_max=int(env("FUGUE_GB_STAGED_MAX", "1200000")),
             parts=parts if parts in (512, 1024, 2048) else 512,
@@ -429,6 +520,9 @@ class _GbKnobs:
             replay_dense=env("FUGUE_GB_REPLAY_DENSE", "1") != "0",
             replay_tile=tile,
             dense_slots=slots if slots in (2048, 4096, 8192) else 4096,
+            replay_bin_parts=bin_parts,
+            bin_slots=bin_slots if bin_slots in (2048, 4096, 8192) else 8192,
+            bin_chunk=bin_chunk if bin_chunk >= 256 else 65536,
         )
 
 
@@ -928,10 +1022,14 @@ def groupby_aggregate(
         )
         # the dense gate and the scatter tile are part of the memo key so
         # an in-process A/B keeps one entry per side
+        # the bin knobs shape the dense layout (tile scatter only)
+        bins = (1, 0, 0)
+        if plan.dense_ok and plan.tile > 0 and knobs.replay_bin_parts > 1:
+            bins = (knobs.replay_bin_parts, knobs.bin_slots, knobs.bin_chunk)
         lkey = (
             packed.data_ptr(), n, plan.num_parts, plan.tsize, plan.narrow,
             plan.dense_ok, plan.tile,
-        )
+        ) + bins
         ent = _layout_get(lkey) if plan.reuse else None
         if isinstance(ent, _DenseLayout):
             # dense replay: groups, counts, output order and every row's
@@ -941,12 +1039,22 @@ def groupby_aggregate(
             # purpose: columns are immutable, and a stable key tensor
             # lets the identity-memoized key stats of a downstream join
             # hit instead of re-running.
-            out_sum = ext.gb_replay_dense(
-                vals=vals, gid=ent.gid, offsets=ent.offsets,
-                group_base=ent.group_base, n_groups=ent.n_groups,
-                chunk=plan.ag_chunk, slots=knobs.dense_slots,
-                tile=ent.tile, rank=ent.rank, dst=ent.dst, pos=ent.pos,
-            )
+            if ent.bin_parts > 1:
+                out_sum = ext.gb_replay_binned(
+                    vals=vals, gid=ent.gid, rank=ent.rank, dst=ent.dst,
+                    bin_offsets=ent.bin_offsets,
+                    bin_group_base=ent.bin_group_base,
+                    bin_chunk_base=ent.bin_chunk_base,
+                    total_chunks=ent.bin_chunks, n_groups=ent.n_groups,
+                    chunk=ent.bin_chunk, slots=ent.bin_slots, tile=ent.tile,
+                )
+            else:
+                out_sum = ext.gb_replay_dense(
+                    vals=vals, gid=ent.gid, offsets=ent.offsets,
+                    group_base=ent.group_base, n_groups=ent.n_groups,
+                    chunk=plan.ag_chunk, slots=knobs.dense_slots,
+                    tile=ent.tile, rank=ent.rank, dst=ent.dst, pos=ent.pos,
+                )
             ent.hits += 1
             return ent.out_keys, {aggs[0][2]: out_sum}, ent.out_count, meta
         if ent is not None:
@@ -966,7 +1074,8 @@ def groupby_aggregate(
             new_ent = None
             if plan.dense_ok:
                 new_ent = _prepare_dense_layout(
-                    ext, packed, pkeys, pos, plan.num_parts, plan.tile
+                    ext, packed, pkeys, pos, plan.num_parts, plan.tile,
+                    *bins
                 )
             if new_ent is None:
                 if plan.narrow == 1:
