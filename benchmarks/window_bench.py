@@ -1,0 +1,169 @@
+"""LAG + running SUM per group: device value windows vs the host path.
+
+``SELECT k, v, LAG(v) OVER w AS p, SUM(v) OVER w AS s`` with ``w =
+(PARTITION BY k ORDER BY v)`` through FugueSQL on one GPU, at the shapes
+of ``take_group_bench.py``.  The device path is ``engine.window_over``
+(one partition sort, then the ``seg_shift`` / ``seg_scan_*`` kernels);
+the host path is what the engine did before it (gather to pandas, the
+SQL executor, H2D), forced here through ``FUGUE_HIP_FORCE_HOST_WINDOW=1``.
+The two paths alternate step by step, every step ends in a device
+synchronise, and both results are compared once per shape.  ``sort_ms``
+is the partition sort alone, timed the same way.  Prints one JSON line
+per shape.
+
+    python benchmarks/window_bench.py [--rows 1000000,4000000]
+        [--groups 1000,1000000] [--steps 5] [--host-steps 3] [--warmup 2]
+
+``--kernels N`` instead runs only the kernels (and a plain copy of the
+bytes they move at the least: 33 B/row for the shift, 24 + 40 B/row for
+the scan's summary and apply) N times on the first shape, for a
+``rocprofv3 --kernel-trace --stats`` run of its own.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import pandas as pd
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from fugue_amd.hip import ops as dops  # noqa: E402
+from fugue_amd.hip.execution_engine import HipExecutionEngine  # noqa: E402
+from fugue_amd.hip.frame import HipDataFrame  # noqa: E402
+from fugue_amd.sql.api import fugue_sql  # noqa: E402
+
+_FORCE_HOST = "FUGUE_HIP_FORCE_HOST_WINDOW"
+_SQL = (
+    "SELECT k, v, LAG(v) OVER (PARTITION BY k ORDER BY v) AS p, "
+    "SUM(v) OVER (PARTITION BY k ORDER BY v) AS s FROM df"
+)
+
+
+def _step(engine, hdf, host: bool):
+    if host:
+        os.environ[_FORCE_HOST] = "1"
+    else:
+        os.environ.pop(_FORCE_HOST, None)
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fugue_sql(_SQL, df=hdf, engine=engine, as_fugue=True)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, res
+    finally:
+        os.environ.pop(_FORCE_HOST, None)
+
+
+def _sort_step(engine, hdf):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pkeys, perm = engine._partition_sort(hdf, ["k"], ["v"], [True], "last")
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, pkeys, perm
+
+
+def _digest(res) -> tuple:
+    pdf = res.as_pandas()
+    return (
+        len(pdf), int(pdf["k"].sum()), float(pdf["p"].sum()),
+        int(pdf["p"].isna().sum()), float(pdf["s"].sum()),
+    )
+
+
+def _frame(engine, n: int, g: int) -> HipDataFrame:
+    rng = np.random.default_rng(n % 1000 + g)
+    pdf = pd.DataFrame(
+        dict(
+            k=rng.integers(0, g, n),
+            # integer-valued and unique: exact sums, no ties
+            v=rng.permutation(n).astype(np.float64),
+            w=rng.integers(0, 1 << 40, n),
+        )
+    )
+    hdf = engine.to_df(pdf)
+    assert isinstance(hdf, HipDataFrame)
+    return hdf
+
+
+def _kernels_only(engine, hdf, reps: int) -> None:
+    _, pkeys, perm = _sort_step(engine, hdf)
+    c = hdf.col("v")
+    n = perm.numel()
+    src = {b: torch.empty(n * b // 16, dtype=torch.int64, device=perm.device)
+           for b in (33, 24, 40)}
+    for _ in range(reps):
+        dops.segmented_shift(perm, pkeys, c, 1)
+        dops.segmented_scan(perm, pkeys, c, "sum")
+        for t in src.values():  # a copy reads and writes half the bytes each
+            t.clone()
+    torch.cuda.synchronize()
+    print(json.dumps(dict(bench="window_kernels", rows=n, reps=reps,
+                          copy_elems={str(b): int(t.numel()) for b, t in src.items()})))
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", default="1000000,4000000,16000000")
+    ap.add_argument("--groups", default="1000,1000000")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--host-steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--kernels", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("window_bench needs a GPU")
+    engine = HipExecutionEngine()
+    rows = [int(x) for x in args.rows.split(",")]
+    groups = [int(x) for x in args.groups.split(",")]
+    if args.kernels > 0:
+        _kernels_only(engine, _frame(engine, rows[0], groups[0]), args.kernels)
+        return
+    for n in rows:
+        for g in groups:
+            hdf = _frame(engine, n, g)
+            before = engine.stats.get("window.device_value")
+            for _ in range(args.warmup):
+                _, dres = _step(engine, hdf, host=False)
+            _, hres = _step(engine, hdf, host=True)
+            assert engine.stats.get("window.device_value") == before + 2 * args.warmup
+            same = _digest(dres) == _digest(hres)
+            dev_ms, host_ms, sort_ms = [], [], []
+            for i in range(max(args.steps, args.host_steps)):
+                if i < args.steps:
+                    dev_ms.append(_step(engine, hdf, host=False)[0])
+                    sort_ms.append(_sort_step(engine, hdf)[0])
+                if i < args.host_steps:
+                    host_ms.append(_step(engine, hdf, host=True)[0])
+            d, h = float(np.median(dev_ms)), float(np.median(host_ms))
+            s = float(np.median(sort_ms))
+            print(
+                json.dumps(
+                    dict(
+                        bench="window_lag_sum",
+                        rows=n,
+                        groups=g,
+                        device_ms=round(d, 3),
+                        device_ms_min=round(min(dev_ms), 3),
+                        device_ms_max=round(max(dev_ms), 3),
+                        sort_ms=round(s, 3),
+                        sort_share=round(s / d, 2),
+                        host_ms=round(h, 3),
+                        host_ms_min=round(min(host_ms), 3),
+                        host_ms_max=round(max(host_ms), 3),
+                        host_over_device=round(h / d, 2),
+                        results_equal=bool(same),
+                        steps=args.steps,
+                        host_steps=args.host_steps,
+                        warmup=args.warmup,
+                    )
+                ),
+                flush=True,
+            )
+
+
+if __name__ == "__main__":
+    main()

@@ -1280,6 +1280,70 @@ std::vector<at::Tensor> seg_take(at::Tensor perm, at::Tensor pkeys,
   return {out, bases};
 }
 
+// One 8-byte value column of a value window (int64 bits or float64, in
+// original row order) and its optional bool validity.
+static const uint8_t* seg_check_value(const at::Tensor& data,
+                                      const c10::optional<at::Tensor>& valid,
+                                      int64_t n) {
+  check_gpu(data, "value column");
+  TORCH_CHECK(data.is_contiguous() && data.numel() == n &&
+                  data.element_size() == 8 &&
+                  (data.scalar_type() == at::kLong ||
+                   data.scalar_type() == at::kDouble),
+              "value column must be contiguous int64/float64 of length n");
+  if (!valid.has_value()) return nullptr;
+  const at::Tensor& v = *valid;
+  check_gpu(v, "value validity");
+  TORCH_CHECK(v.scalar_type() == at::kBool && v.is_contiguous() &&
+                  v.numel() == n,
+              "validity must be contiguous bool of length n");
+  return reinterpret_cast<const uint8_t*>(v.data_ptr());
+}
+
+// LAG/LEAD: row i takes the value `offset` sorted positions back (ahead
+// when negative) if that row is in its partition.  Returns (data, valid)
+// in original row order; data keeps the input dtype.
+std::vector<at::Tensor> seg_shift(at::Tensor perm, at::Tensor pkeys,
+                                  at::Tensor data,
+                                  c10::optional<at::Tensor> valid,
+                                  int64_t offset) {
+  seg_check_inputs(perm, pkeys);
+  int64_t n = perm.numel();
+  const uint8_t* vp = seg_check_value(data, valid, n);
+  auto out = at::empty_like(data);
+  auto out_valid = at::empty({n}, perm.options().dtype(at::kBool));
+  launch_seg_shift(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(),
+                   reinterpret_cast<const int64_t*>(data.data_ptr()), vp, n,
+                   offset, reinterpret_cast<int64_t*>(out.data_ptr()),
+                   reinterpret_cast<uint8_t*>(out_valid.data_ptr()),
+                   current_stream());
+  return {out, out_valid};
+}
+
+// Running SUM (op 0) / MIN (1) / MAX (2) of the non-null values from the
+// partition's first sorted position to each row, and their count.
+// Returns (acc in the input dtype, cnt int64) in original row order.
+std::vector<at::Tensor> seg_scan(at::Tensor perm, at::Tensor pkeys,
+                                 at::Tensor data,
+                                 c10::optional<at::Tensor> valid, int64_t op) {
+  seg_check_inputs(perm, pkeys);
+  int64_t n = perm.numel();
+  const uint8_t* vp = seg_check_value(data, valid, n);
+  TORCH_CHECK(op >= 0 && op <= 2, "op must be 0, 1 or 2");
+  auto acc = at::empty_like(data);
+  auto cnt = at::empty({n}, perm.options());
+  if (n == 0) return {acc, cnt};
+  int64_t nblocks = (n + SEG_CHUNK - 1) / SEG_CHUNK;
+  auto work = at::empty({6 * nblocks}, perm.options());
+  launch_seg_scan(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(),
+                  reinterpret_cast<const int64_t*>(data.data_ptr()), vp, n,
+                  (int)op, data.is_floating_point() ? 1 : 0,
+                  work.data_ptr<int64_t>(),
+                  reinterpret_cast<int64_t*>(acc.data_ptr()),
+                  cnt.data_ptr<int64_t>(), current_stream());
+  return {acc, cnt};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // limits the python layer plans by (ops.py keeps copies for hosts
   // without the extension; a GPU test compares them)
@@ -1366,6 +1430,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "segmented row_number/rank/dense_rank in original row order");
   m.def("seg_take", &seg_take,
         "deterministic first-n-per-segment index vector");
+  m.def("seg_shift", &seg_shift,
+        "segment-bounded shift (LAG/LEAD) in original row order");
+  m.def("seg_scan", &seg_scan,
+        "segmented running sum/min/max + non-null count");
   m.def("gb_compact", &gb_compact,
         "deterministic group-table compaction");
   m.def("compact_columns_cap", &compact_columns_cap,

@@ -256,5 +256,13 @@ void launch_seg_rank(const int64_t* perm, const int64_t* pkeys,
 void launch_seg_take(const int64_t* perm, const int64_t* pkeys, int64_t n,
                      int64_t n_take, int64_t* work, int64_t* bcounts,
                      int64_t* bases, int64_t* out, hipStream_t stream);
+void launch_seg_shift(const int64_t* perm, const int64_t* pkeys,
+                      const int64_t* vals, const uint8_t* valid, int64_t n,
+                      int64_t d, int64_t* out, uint8_t* out_valid,
+                      hipStream_t stream);
+void launch_seg_scan(const int64_t* perm, const int64_t* pkeys,
+                     const int64_t* vals, const uint8_t* valid, int64_t n,
+                     int op, int is_float, int64_t* work, int64_t* out_acc,
+                     int64_t* out_cnt, hipStream_t stream);
 
 }  // extern "C"

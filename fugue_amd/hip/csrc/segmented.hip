@@ -486,6 +486,285 @@ __global__ __launch_bounds__(BLOCK) void seg_take_emit_kernel(
   }
 }
 
+// ------------------------------------------------------------------ //
+// value windows over the same sorted permutation                       //
+//                                                                      //
+// seg_shift: LAG/LEAD, a segment-bounded shift of one 8-byte column.   //
+// seg_scan: running SUM/MIN/MAX and COUNT of the non-null values from  //
+// the partition's first sorted position to the current one.  vals and  //
+// valid are in original row order and gathered through perm; results   //
+// land in original row order (out[perm[i]]).  The scan chains its      //
+// chunks like the rank: summary -> single-block scan -> apply.         //
+// ------------------------------------------------------------------ //
+
+// Precondition: perm sorts by partition key first, so equal keys are
+// contiguous and "the row d positions back has my key" means "it is in
+// my partition".  d > 0 looks back (LAG), d < 0 ahead (LEAD); the
+// launcher clamps d to [-n, n].  Moves bits only.
+__global__ __launch_bounds__(BLOCK) void seg_shift_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
+    int64_t n, int64_t d, int64_t* __restrict__ out,
+    uint8_t* __restrict__ out_valid) {
+  int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  int64_t j = seg_row(perm, i, n);
+  int64_t s = i - d;
+  int64_t v = 0;
+  uint8_t ok = 0;
+  if (s >= 0 && s < n) {
+    int64_t js = seg_row(perm, s, n);
+    if (pkeys[js] == pkeys[j]) {
+      v = vals[js];
+      ok = valid != nullptr ? (uint8_t)(valid[js] != 0) : (uint8_t)1;
+    }
+  }
+  out[j] = v;
+  out_valid[j] = ok;
+}
+
+#define SEG_OP_SUM 0
+#define SEG_OP_MIN 1
+#define SEG_OP_MAX 2
+
+// Scan element of a range of sorted positions: head says the range holds
+// a partition start, and then acc/cnt cover the positions from the LAST
+// start on; otherwise they cover the whole range.  cnt is the number of
+// non-null values folded into acc; cnt == 0 is the identity (acc is 0
+// then), so MIN and MAX need no sentinel value.
+struct SegVal {
+  int head;
+  int64_t acc;  // int64, or the bits of a double
+  int64_t cnt;
+};
+
+__device__ __forceinline__ SegVal seg_val_identity() {
+  SegVal r;
+  r.head = 0;
+  r.acc = 0;
+  r.cnt = 0;
+  return r;
+}
+
+// op of two non-empty sides.  Integer SUM adds unsigned: overflow wraps.
+// NaN never arrives here (the caller passes it as null).
+__device__ __forceinline__ int64_t seg_val_op(int64_t a, int64_t b, int op,
+                                              int is_float) {
+  if (is_float) {
+    double x = __longlong_as_double(a), y = __longlong_as_double(b);
+    double r = op == SEG_OP_SUM ? x + y
+                                : (op == SEG_OP_MIN ? (y < x ? y : x)
+                                                    : (y > x ? y : x));
+    return __double_as_longlong(r);
+  }
+  if (op == SEG_OP_SUM) return (int64_t)((uint64_t)a + (uint64_t)b);
+  if (op == SEG_OP_MIN) return b < a ? b : a;
+  return b > a ? b : a;
+}
+
+__device__ __forceinline__ SegVal seg_val_combine(SegVal a, SegVal b, int op,
+                                                  int is_float) {
+  if (b.head) return b;
+  SegVal r;
+  r.head = a.head;
+  r.cnt = a.cnt + b.cnt;
+  r.acc = a.cnt == 0 ? b.acc
+                     : (b.cnt == 0 ? a.acc
+                                   : seg_val_op(a.acc, b.acc, op, is_float));
+  return r;
+}
+
+// Inclusive segmented scan of x over this iteration's 256 positions,
+// continued from carry (everything before them), which is advanced past
+// them.  Each wave scans its 64 lanes with shuffles; wave totals meet in
+// ws (double-buffered by the caller: one barrier per call).  The combine
+// tree depends on the position alone, so a rerun repeats every bit.
+// Block-uniform call.
+__device__ __forceinline__ SegVal seg_val_block_step(SegVal x, int lane,
+                                                     int wave, int op,
+                                                     int is_float,
+                                                     SegVal& carry,
+                                                     SegVal* ws) {
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    SegVal t;
+    t.head = __shfl_up(x.head, off);
+    t.acc = __shfl_up(x.acc, off);
+    t.cnt = __shfl_up(x.cnt, off);
+    if (lane >= off) x = seg_val_combine(t, x, op, is_float);
+  }
+  if (lane == WAVE - 1) ws[wave] = x;
+  __syncthreads();
+  SegVal in = carry;
+  SegVal tot = carry;
+#pragma unroll
+  for (int w = 0; w < SEG_WAVES; ++w) {
+    SegVal s = ws[w];
+    if (w < wave) in = seg_val_combine(in, s, op, is_float);
+    tot = seg_val_combine(tot, s, op, is_float);
+  }
+  carry = tot;
+  return seg_val_combine(in, x, op, is_float);
+}
+
+// scan element of sorted position i (identity past the end); j is its
+// row.  Must be called by every lane of the wave.
+__device__ __forceinline__ SegVal seg_val_load(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const SegCols& none, const int64_t* __restrict__ vals,
+    const uint8_t* __restrict__ valid, int64_t i, int64_t n, int lane,
+    int64_t& j) {
+  bool h, p;
+  seg_flags(perm, pkeys, none, 0, i, n, lane, j, h, p);
+  SegVal x = seg_val_identity();
+  if (i < n) {
+    bool ok = valid == nullptr || valid[j] != 0;
+    x.head = h ? 1 : 0;
+    x.cnt = ok ? 1 : 0;
+    x.acc = ok ? vals[j] : 0;
+  }
+  return x;
+}
+
+// per-chunk aggregate, folded in the same order as the apply kernel
+__global__ __launch_bounds__(BLOCK) void seg_scan_summary_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
+    int64_t n, int op, int is_float, int64_t* __restrict__ sum_head,
+    int64_t* __restrict__ sum_acc, int64_t* __restrict__ sum_cnt) {
+  __shared__ SegVal ws[2][SEG_WAVES];
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  int wave = threadIdx.x / WAVE;
+  SegCols none;
+  memset(&none, 0, sizeof(none));
+  SegVal carry = seg_val_identity();  // same value in every thread
+  for (int it = 0; it < SEG_ITERS; ++it) {
+    int64_t i0 = start + (int64_t)it * BLOCK;
+    if (i0 >= n) break;  // block-uniform
+    int64_t j;
+    SegVal x = seg_val_load(perm, pkeys, none, vals, valid,
+                            i0 + threadIdx.x, n, lane, j);
+    seg_val_block_step(x, lane, wave, op, is_float, carry, ws[it & 1]);
+  }
+  if (threadIdx.x == 0) {
+    sum_head[blockIdx.x] = carry.head;
+    sum_acc[blockIdx.x] = carry.acc;
+    sum_cnt[blockIdx.x] = carry.cnt;
+  }
+}
+
+// single-block exclusive segmented scan of the chunk aggregates: chunk b
+// receives the aggregate of chunks [0, b)
+__global__ __launch_bounds__(BLOCK) void seg_scan_scan_kernel(
+    const int64_t* __restrict__ sum_head, const int64_t* __restrict__ sum_acc,
+    const int64_t* __restrict__ sum_cnt, int nblocks, int op, int is_float,
+    int64_t* __restrict__ car_head, int64_t* __restrict__ car_acc,
+    int64_t* __restrict__ car_cnt) {
+  __shared__ SegVal tile[BLOCK];
+  SegVal carry = seg_val_identity();  // same value in every thread
+  for (int t0 = 0; t0 < nblocks; t0 += BLOCK) {
+    int i = t0 + (int)threadIdx.x;
+    SegVal v = seg_val_identity();
+    if (i < nblocks) {
+      v.head = (int)sum_head[i];
+      v.acc = sum_acc[i];
+      v.cnt = sum_cnt[i];
+    }
+    tile[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 1; off < BLOCK; off <<= 1) {
+      SegVal self = tile[threadIdx.x];
+      bool has = (int)threadIdx.x >= off;
+      SegVal left = self;
+      if (has) left = tile[threadIdx.x - off];
+      __syncthreads();
+      if (has) tile[threadIdx.x] = seg_val_combine(left, self, op, is_float);
+      __syncthreads();
+    }
+    if (i < nblocks) {
+      SegVal e = carry;
+      if (threadIdx.x > 0)
+        e = seg_val_combine(carry, tile[threadIdx.x - 1], op, is_float);
+      car_head[i] = e.head;
+      car_acc[i] = e.acc;
+      car_cnt[i] = e.cnt;
+    }
+    carry = seg_val_combine(carry, tile[BLOCK - 1], op, is_float);
+    __syncthreads();
+  }
+}
+
+// writes acc and cnt of every row, null rows included (they carry the
+// running value through; acc is 0 while cnt is 0)
+__global__ __launch_bounds__(BLOCK) void seg_scan_apply_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
+    int64_t n, int op, int is_float, const int64_t* __restrict__ car_head,
+    const int64_t* __restrict__ car_acc, const int64_t* __restrict__ car_cnt,
+    int64_t* __restrict__ out_acc, int64_t* __restrict__ out_cnt) {
+  __shared__ SegVal ws[2][SEG_WAVES];
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  int wave = threadIdx.x / WAVE;
+  SegCols none;
+  memset(&none, 0, sizeof(none));
+  SegVal carry;
+  carry.head = (int)car_head[blockIdx.x];
+  carry.acc = car_acc[blockIdx.x];
+  carry.cnt = car_cnt[blockIdx.x];
+  for (int it = 0; it < SEG_ITERS; ++it) {
+    int64_t i0 = start + (int64_t)it * BLOCK;
+    if (i0 >= n) break;  // block-uniform
+    int64_t i = i0 + threadIdx.x;
+    int64_t j;
+    SegVal x = seg_val_load(perm, pkeys, none, vals, valid, i, n, lane, j);
+    SegVal r =
+        seg_val_block_step(x, lane, wave, op, is_float, carry, ws[it & 1]);
+    if (i < n) {
+      out_acc[j] = r.acc;
+      out_cnt[j] = r.cnt;
+    }
+  }
+}
+
+extern "C" {
+
+void launch_seg_shift(const int64_t* perm, const int64_t* pkeys,
+                      const int64_t* vals, const uint8_t* valid, int64_t n,
+                      int64_t d, int64_t* out, uint8_t* out_valid,
+                      hipStream_t stream) {
+  if (n <= 0) return;
+  // |d| >= n never finds a source; clamping keeps i - d from overflowing
+  d = d > n ? n : (d < -n ? -n : d);
+  int64_t nblocks = (n + BLOCK - 1) / BLOCK;
+  hipLaunchKernelGGL(seg_shift_kernel, dim3((unsigned)nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, vals, valid, n, d, out, out_valid);
+}
+
+// work: 6 * nblocks int64 (chunk aggregates, then chunk carries)
+void launch_seg_scan(const int64_t* perm, const int64_t* pkeys,
+                     const int64_t* vals, const uint8_t* valid, int64_t n,
+                     int op, int is_float, int64_t* work, int64_t* out_acc,
+                     int64_t* out_cnt, hipStream_t stream) {
+  if (n <= 0) return;
+  int nblocks = (int)((n + SEG_CHUNK - 1) / SEG_CHUNK);
+  int64_t* w = work;
+  hipLaunchKernelGGL(seg_scan_summary_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, vals, valid, n, op, is_float, w,
+                     w + nblocks, w + 2 * (int64_t)nblocks);
+  hipLaunchKernelGGL(seg_scan_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, w,
+                     w + nblocks, w + 2 * (int64_t)nblocks, nblocks, op,
+                     is_float, w + 3 * (int64_t)nblocks,
+                     w + 4 * (int64_t)nblocks, w + 5 * (int64_t)nblocks);
+  hipLaunchKernelGGL(seg_scan_apply_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, vals, valid, n, op, is_float,
+                     w + 3 * (int64_t)nblocks, w + 4 * (int64_t)nblocks,
+                     w + 5 * (int64_t)nblocks, out_acc, out_cnt);
+}
+
+}  // extern "C"
+
 extern "C" {
 
 static SegCols seg_make_cols(const int64_t* const* col_data,

@@ -1711,6 +1711,187 @@ class HipExecutionEngine(ExecutionEngine):
         self._stats.add("window.device")
         return HipDataFrame.from_columns(cols, schema, self._device)
 
+    _VALUE_WINDOW_FUNCS = ("lag", "lead", "sum", "min", "max", "count", "avg")
+
+    def _check_value_items(
+        self, d: HipDataFrame, order_names: List[str], items: List[Any]
+    ) -> bool:
+        """Checks of ``window_over`` that read the schema and the arguments
+        only.  Returns whether some item reads an integer column: those
+        additionally depend on the column carrying a validity mask."""
+        names = set()
+        any_int = False
+        for name, func, arg, offset, default in items:
+            if func not in self._VALUE_WINDOW_FUNCS:
+                raise NotImplementedError(f"window function {func}")
+            if name in d.schema or name in names:
+                raise NotImplementedError(f"column {name} already exists")
+            names.add(name)
+            if func not in ("lag", "lead") and len(order_names) == 0:
+                raise NotImplementedError("aggregate window without ORDER BY")
+            if arg is None:
+                if func != "count":
+                    raise NotImplementedError(f"{func} needs an argument")
+                continue
+            if arg not in d.schema:
+                raise NotImplementedError(f"column {arg} not in the frame")
+            tp = d.schema[arg].type
+            is_int = pa.types.is_signed_integer(tp)
+            if not (is_int or pa.types.is_floating(tp)) or isinstance(
+                d.col(arg), StringDeviceColumn
+            ):
+                # strings, nested, bool, dates: the host's types differ
+                raise NotImplementedError(f"window over a {tp} column")
+            any_int |= is_int
+            if func == "sum" and tp == pa.float32():
+                # pandas accumulates a float32 cumsum in float32
+                raise NotImplementedError("running sum of a float column")
+            if func in ("lag", "lead"):
+                offset = 1 if offset is None else offset
+                if isinstance(offset, bool) or not isinstance(offset, int):
+                    raise NotImplementedError("LAG/LEAD offset not an integer")
+                if offset < 0:
+                    raise NotImplementedError("negative LAG/LEAD offset")
+                if default is not None and (
+                    isinstance(default, bool)
+                    or not isinstance(default, (int, float))
+                    or default != default
+                ):
+                    raise NotImplementedError("LAG/LEAD default")
+        return any_int
+
+    def window_over(
+        self,
+        df: DataFrame,
+        partition_by: List[str],
+        order_by: List[Tuple[str, bool]],
+        items: List[Tuple[str, str, Optional[str], Optional[int], Any]],
+    ) -> DataFrame:
+        """``df`` plus one value-window column per item, all over
+        (PARTITION BY ``partition_by`` ORDER BY ``order_by``); nulls sort
+        last and ties keep original row order.  Each item is ``(name,
+        func, arg_column, offset, default)`` with ``func`` in ``lag`` /
+        ``lead`` / ``sum`` / ``min`` / ``max`` / ``count`` / ``avg``.
+        ``offset`` (default 1) and ``default`` belong to ``lag``/``lead``;
+        ``count`` with ``arg_column=None`` is ``COUNT(*)``.  Aggregates run
+        from the partition's first row to the current one and do not merge
+        peers.  Values and types are the host SQL executor's (table in
+        ``sql/planner.py``).  Raises ``NotImplementedError`` for shapes
+        that stay on the host."""
+        d = self.to_df(df)
+        if not isinstance(d, HipDataFrame):
+            raise NotImplementedError("window_over needs a device frame")
+        if os.environ.get("FUGUE_HIP_FORCE_HOST_WINDOW", "") == "1":
+            # A/B probe (benchmarks/window_bench.py): the host path
+            raise NotImplementedError("host window forced")
+        if len(partition_by) == 0:
+            raise NotImplementedError("window without PARTITION BY")
+        if len(items) == 0:
+            raise NotImplementedError("no window items")
+        order_names = [c for c, _ in order_by]
+        order_asc = [bool(a) for _, a in order_by]
+        keys = list(partition_by)
+        items = [tuple(it) for it in items]
+        any_int = self._check_value_items(d, order_names, items)
+        self._check_rank_shape(d, keys, order_names)
+        if any_int:
+            # The host reads an integer column that carries a validity
+            # mask as a nullable (or float) series and types its windows
+            # differently; that stays there.  The mask is per shard, so
+            # the ranks agree on the answer first.
+            masked = int(
+                any(
+                    it[2] is not None
+                    and pa.types.is_integer(d.schema[it[2]].type)
+                    and d.col(it[2]).valid is not None
+                    for it in items
+                )
+            )
+            if self.is_distributed:
+                masked = int(self._comm.allreduce_sum(masked))
+            if masked > 0:
+                raise NotImplementedError("nullable integer window column")
+        total = d.count()
+        if self.is_distributed:
+            total = int(self._comm.allreduce_sum(total))
+        if total == 0:
+            # the host executor types an empty window column as double
+            raise NotImplementedError("window over an empty frame")
+        from fugue_amd.hip.frame import _torch_dtype_for
+
+        new_cols: Dict[str, DeviceColumn] = {}
+        with op_range("fugue.window.value"):
+            if self.is_distributed:
+                d = self._shuffle_by_columns(d, keys)
+            pkeys, perm = self._partition_sort(
+                d, keys, order_names, order_asc, "last"
+            )
+            scans: Dict[Tuple[str, str], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+            def _scan(arg: str, func: str, as_double: bool = False):
+                key = (arg, func + ("/f64" if as_double else ""))
+                if key not in scans:
+                    c = d.col(arg)
+                    col: Any = c
+                    if as_double:
+                        col = (c.data.to(torch.float64), c.valid)
+                    scans[key] = dops.segmented_scan(perm, pkeys, col, func)
+                return scans[key]
+
+            for name, func, arg, offset, default in items:
+                if arg is None:  # COUNT(*) with ORDER BY is row_number
+                    rn = dops.segmented_rank(perm, pkeys, [], "row_number")
+                    new_cols[name] = DeviceColumn(rn, None, pa.int64())
+                    continue
+                c = d.col(arg)
+                tp = d.schema[arg].type
+                in_valid = c.valid
+                if c.data.is_floating_point():
+                    notnan = ~torch.isnan(c.data)
+                    in_valid = notnan if in_valid is None else in_valid & notnan
+                if func in ("lag", "lead"):
+                    k = 1 if offset is None else int(offset)
+                    data, valid = dops.segmented_shift(
+                        perm, pkeys, c, k if func == "lag" else -k
+                    )
+                    if k == 0 or pa.types.is_floating(tp):
+                        out_tp = tp  # shift(0) adds no NaN: type kept
+                    else:
+                        out_tp = pa.float64()  # pandas shift: int -> float
+                    data = data.to(_torch_dtype_for(out_tp))
+                    out_valid: Optional[torch.Tensor] = valid
+                    if not data.is_floating_point():
+                        out_valid = None  # k == 0 of a null-free column
+                    elif default is not None:
+                        # fillna: a null source value is replaced as well
+                        fill = torch.full_like(data, default)
+                        data = torch.where(valid, data, fill)
+                        out_valid = None
+                    new_cols[name] = DeviceColumn(data, out_valid, out_tp)
+                elif func in ("sum", "min", "max"):
+                    acc, _ = _scan(arg, func)
+                    new_cols[name] = DeviceColumn(
+                        acc.to(c.data.dtype), in_valid, tp
+                    )
+                elif func == "count":
+                    _, cnt = _scan(arg, "sum")
+                    new_cols[name] = DeviceColumn(
+                        cnt.to(torch.float64), None, pa.float64()
+                    )
+                else:  # avg: float64 sum of the converted values / count
+                    acc, cnt = _scan(arg, "sum", as_double=True)
+                    some = cnt > 0
+                    mean = acc / torch.where(some, cnt, torch.ones_like(cnt))
+                    new_cols[name] = DeviceColumn(mean, some, pa.float64())
+        cols = dict(d.columns_map)
+        cols.update(new_cols)
+        schema = d.schema + Schema(
+            [(n, c.pa_type) for n, c in new_cols.items()]
+        )
+        for _ in items:
+            self._stats.add("window.device_value")
+        return HipDataFrame.from_columns(cols, schema, self._device)
+
     # ------------------------------------------------------------------ #
     # select / aggregate: device fast path                                 #
     # ------------------------------------------------------------------ #

@@ -1746,6 +1746,145 @@ def segmented_rank(
     )
 
 
+SCAN_FUNCS = {"sum": 0, "min": 1, "max": 2}
+
+
+def _value_col_parts(c: Any) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(8-byte data, validity) of a window value column; a NaN counts as
+    null, as it does for the host executor."""
+    data, valid = _order_col_parts(c)
+    if data.is_floating_point():
+        notnan = ~torch.isnan(data)
+        valid = notnan if valid is None else (valid & notnan)
+    return data, valid
+
+
+def _segmented_shift_cpu(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    data: torch.Tensor,
+    valid: Optional[torch.Tensor],
+    offset: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Shifted (data, valid) per SORTED position."""
+    n = perm.numel()
+    pos = torch.arange(n, dtype=torch.int64)
+    src = pos - max(-n, min(n, offset))
+    inside = (src >= 0) & (src < n)
+    srcc = torch.where(inside, src, pos)
+    ks = pkeys.index_select(0, perm)
+    inside &= ks.index_select(0, srcc) == ks
+    rows = perm.index_select(0, srcc)
+    ok = inside
+    if valid is not None:
+        ok = inside & valid.index_select(0, rows)
+    v = data.index_select(0, rows)
+    return torch.where(inside, v, torch.zeros_like(v)), ok
+
+
+def segmented_shift(
+    perm: torch.Tensor, pkeys: torch.Tensor, col: Any, offset: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``LAG`` (``offset > 0``) / ``LEAD`` (``offset < 0``) of one value
+    column inside its partition: ``(data, valid)`` in ORIGINAL row order,
+    where row ``perm[i]`` holds the value of row ``perm[i - offset]`` and
+    is valid iff that position exists, lies in the same partition and
+    holds a non-null value.  Inputs as :func:`segmented_rank`; ``col`` is
+    a ``DeviceColumn`` or a ``(data, valid)`` pair.  ``data`` comes back
+    widened to int64/float64 and is 0 where the partition has no source
+    row."""
+    data, valid = _value_col_parts(col)
+    perm = perm.contiguous()
+    pkeys = pkeys.contiguous()
+    offset = int(offset)
+    if _is_cpu(perm):
+        n = perm.numel()
+        out = torch.empty_like(data)
+        out_valid = torch.empty(n, dtype=torch.bool)
+        if n > 0:
+            d, v = _segmented_shift_cpu(perm, pkeys, data, valid, offset)
+            out[perm] = d
+            out_valid[perm] = v
+        return out, out_valid
+    n = perm.numel()
+    offset = max(-n, min(n, offset))  # beyond ±n nothing has a source
+    out, out_valid = get_ext().seg_shift(perm, pkeys, data, valid, offset)
+    return out, out_valid
+
+
+def _segmented_scan_cpu(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    data: torch.Tensor,
+    valid: Optional[torch.Tensor],
+    op: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(acc, cnt) per SORTED position: a segmented Hillis-Steele scan, so
+    a float sum only ever adds values of its own partition."""
+    n = perm.numel()
+    head, _ = _segment_flags_cpu(perm, pkeys, [])
+    acc = data.index_select(0, perm)
+    if valid is not None:
+        ok = valid.index_select(0, perm)
+        acc = torch.where(ok, acc, torch.zeros_like(acc))
+        cnt = ok.to(torch.int64)
+    else:
+        cnt = torch.ones(n, dtype=torch.int64)
+    pos = torch.arange(n, dtype=torch.int64)
+    seg_start = torch.cummax(torch.where(head, pos, torch.zeros_like(pos)), 0).values
+    longest = int((pos - seg_start).max().item()) + 1
+    flag = head.clone()
+    off = 1
+    while off < longest:
+        la, lc, lf = acc[:-off], cnt[:-off], flag[:-off]
+        ra, rc, rf = acc[off:], cnt[off:], flag[off:]
+        if op == 0:
+            both = la + ra  # int64 wraps like the unsigned device add
+        elif op == 1:
+            both = torch.where(ra < la, ra, la)
+        else:
+            both = torch.where(ra > la, ra, la)
+        merged = torch.where(lc == 0, ra, torch.where(rc == 0, la, both))
+        new_acc = torch.where(rf, ra, merged)
+        new_cnt = torch.where(rf, rc, lc + rc)
+        new_flag = rf | lf
+        acc = torch.cat([acc[:off], new_acc])
+        cnt = torch.cat([cnt[:off], new_cnt])
+        flag = torch.cat([flag[:off], new_flag])
+        off <<= 1
+    return acc, cnt
+
+
+def segmented_scan(
+    perm: torch.Tensor, pkeys: torch.Tensor, col: Any, func: str
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Running ``sum`` / ``min`` / ``max`` of one value column from the
+    first sorted position of the row's partition to the row itself (ROWS
+    UNBOUNDED PRECEDING .. CURRENT ROW; peers are not merged).  Returns
+    ``(acc, cnt)`` in ORIGINAL row order: ``cnt`` (int64) is the number of
+    non-null values folded so far and ``acc`` (int64 or float64) their
+    aggregate, 0 while ``cnt`` is 0.  A null row carries the running value
+    through; the caller decides the validity of its result.  Integer sums
+    wrap.  Inputs as :func:`segmented_shift`."""
+    if func not in SCAN_FUNCS:
+        raise ValueError(f"unknown scan function {func!r}")
+    op = SCAN_FUNCS[func]
+    data, valid = _value_col_parts(col)
+    perm = perm.contiguous()
+    pkeys = pkeys.contiguous()
+    if _is_cpu(perm):
+        n = perm.numel()
+        acc = torch.empty_like(data)
+        cnt = torch.empty(n, dtype=torch.int64)
+        if n > 0:
+            a, c = _segmented_scan_cpu(perm, pkeys, data, valid, op)
+            acc[perm] = a
+            cnt[perm] = c
+        return acc, cnt
+    acc, cnt = get_ext().seg_scan(perm, pkeys, data, valid, op)
+    return acc, cnt
+
+
 def take_per_group_indices(
     perm: torch.Tensor, pkeys: torch.Tensor, n: int
 ) -> torch.Tensor:

@@ -365,6 +365,129 @@ def _find_ranking_window(
     return found[0], kind, pcols, ocols
 
 
+_VALUE_TMP = "_fugue_window_value_"  # + the select index of the item
+
+# Value windows the engine computes with its segmented shift and scan
+# kernels (``engine.window_over``).  With ORDER BY the aggregates are
+# running ones.  Result types measured on ``executor.WindowFunc.eval``
+# for a null-free integer column / a double column (nulls allowed) / a
+# float column:
+#
+#   function            byte,short,int,long   double    float
+#   LAG/LEAD(x, k>=1)   double                double    float
+#   LAG/LEAD(x, 0)      the input type        double    float
+#   SUM MIN MAX         the input type        double    float
+#   COUNT(x)            double                double    double
+#   AVG(x)              double                double    double
+#   COUNT(*)            long                  long      long
+#
+# LAG/LEAD go through ``shift``, which turns integers into float64 as
+# soon as one row has no source (k >= 1 on a non-empty frame); a default
+# (``fillna``) does not turn them back.  SUM is ``cumsum`` in the input
+# type (int sums wrap); COUNT(x) and AVG are ``expanding().count()`` /
+# ``.mean()``, always float64.  An integer column that carries nulls
+# reaches the executor as a nullable or float series with other result
+# types, a float SUM accumulates in float32 and a bool column keeps bool:
+# ``window_over`` declines those, and the statement falls back.
+_VALUE_WINDOWS = {
+    "LAG": "lag",
+    "LEAD": "lead",
+    "SUM": "sum",
+    "MIN": "min",
+    "MAX": "max",
+    "COUNT": "count",
+    "AVG": "avg",
+    "MEAN": "avg",
+}
+
+
+def _window_over_clause(
+    w: X.WindowFunc, schema: Schema
+) -> Tuple[List[str], List[Tuple[str, bool]]]:
+    pcols: List[str] = []
+    for e in w.partition_by:
+        if not isinstance(e, X.ColRef) or e.name not in schema:
+            raise UnsupportedPlan("PARTITION BY expression")
+        pcols.append(e.name)
+    if len(pcols) == 0:
+        raise UnsupportedPlan("window without PARTITION BY")
+    ocols: List[Tuple[str, bool]] = []
+    for o in w.order_by:
+        if not isinstance(o.expr, X.ColRef) or o.expr.name not in schema:
+            raise UnsupportedPlan("window ORDER BY expression")
+        ocols.append((o.expr.name, bool(o.asc)))
+    return pcols, ocols
+
+
+def _find_value_windows(
+    stmt: X.SelectStmt, schema: Schema
+) -> Optional[Tuple[List[str], List[Tuple[str, bool]], Dict[int, Tuple]]]:
+    """(partition columns, order (column, asc) pairs, {select index:
+    ``window_over`` item}) when every window item of the statement is a
+    value window and all share one OVER clause.  None when the select list
+    has no value window (ranking windows are looked for next); raises
+    UnsupportedPlan for a value window outside the lowering."""
+    found = [
+        i for i, (e, _a) in enumerate(stmt.columns)
+        if isinstance(e, X.WindowFunc)
+    ]
+    if not any(
+        stmt.columns[i][0].func.name in _VALUE_WINDOWS for i in found
+    ):
+        return None
+    if stmt.group_by or stmt.having is not None or stmt.distinct:
+        raise UnsupportedPlan("window with GROUP BY/HAVING/DISTINCT")
+    if stmt.joins:
+        raise UnsupportedPlan("window over a join")
+    over: Optional[Tuple[List[str], List[Tuple[str, bool]]]] = None
+    items: Dict[int, Tuple] = {}
+    for i in found:
+        w = stmt.columns[i][0]
+        func = _VALUE_WINDOWS.get(w.func.name)
+        if func is None or w.func.distinct:
+            raise UnsupportedPlan(f"window function {w.func.name}")
+        this = _window_over_clause(w, schema)
+        if over is not None and this != over:
+            raise UnsupportedPlan("window items with different OVER clauses")
+        over = this
+        args = w.func.args
+        if len(args) == 0 or len(args) > (3 if func in ("lag", "lead") else 1):
+            raise UnsupportedPlan(f"{w.func.name} with {len(args)} args")
+        arg: Optional[str] = None
+        if isinstance(args[0], X.Star):
+            if func != "count":
+                raise UnsupportedPlan(f"{w.func.name}(*)")
+        elif isinstance(args[0], X.ColRef) and args[0].name in schema:
+            arg = args[0].name
+        else:
+            raise UnsupportedPlan("window argument expression")
+        if func not in ("lag", "lead") and len(this[1]) == 0:
+            raise UnsupportedPlan("whole-partition aggregate window")
+        k: Optional[int] = None
+        default: Any = None
+        if len(args) > 1:
+            if not isinstance(args[1], X.Lit):
+                raise UnsupportedPlan("LAG/LEAD offset is not a literal")
+            k = args[1].value
+            if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+                raise UnsupportedPlan("LAG/LEAD offset")
+        if len(args) > 2:
+            if not isinstance(args[2], X.Lit):
+                raise UnsupportedPlan("LAG/LEAD default is not a literal")
+            default = args[2].value
+            if default is not None and (
+                isinstance(default, bool)
+                or not isinstance(default, (int, float))
+            ):
+                raise UnsupportedPlan("LAG/LEAD default")
+        name = f"{_VALUE_TMP}{i}"
+        if name in schema:
+            raise UnsupportedPlan("reserved column name in input")
+        items[i] = (name, func, arg, k, default)
+    assert over is not None
+    return over[0], over[1], items
+
+
 def _execute_core(
     stmt: X.SelectStmt, tables: Dict[str, DataFrame], engine: Any
 ) -> DataFrame:
@@ -496,7 +619,22 @@ def _execute_core(
     cols: List[ColumnExpr] = []
     from fugue_amd.column.expressions import all_cols
 
-    window = _find_ranking_window(stmt, schema)
+    value_windows = _find_value_windows(stmt, schema)
+    value_items: Dict[int, Tuple] = {}
+    if value_windows is not None:
+        # WHERE filters the rows the windows see, so it runs first
+        if where_expr is not None:
+            res = engine.select(
+                res, SelectColumns(all_cols()), where=where_expr
+            )
+            where_expr = None
+        pcols, ocols, value_items = value_windows
+        res = engine.window_over(
+            res, pcols, ocols, [value_items[i] for i in sorted(value_items)]
+        )
+        window = None
+    else:
+        window = _find_ranking_window(stmt, schema)
     if window is not None:
         # WHERE filters the rows the window sees, so it runs first
         if where_expr is not None:
@@ -510,15 +648,20 @@ def _execute_core(
         if isinstance(e, X.Star):
             if e.qualifier is not None:
                 raise UnsupportedPlan("qualified * in select")
-            if window is not None:
-                # the pre-window columns only: the rank column is
-                # projected under its own name below
+            if window is not None or value_items:
+                # the pre-window columns only: the window columns are
+                # projected under their own names below
                 cols.extend(col(n) for n in schema.names)
             else:
                 cols.append(all_cols())
             continue
         if window is not None and i == window[0]:
             cols.append(col(_WINDOW_TMP).alias(alias or e.default_name()))
+            continue
+        if i in value_items:
+            cols.append(
+                col(value_items[i][0]).alias(alias or e.default_name())
+            )
             continue
         ce = _to_column_expr(e, schema, {})
         name = alias or e.default_name() or f"_col{i}"
