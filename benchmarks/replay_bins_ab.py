@@ -28,6 +28,9 @@ def _select(env):
     for name in _KNOBS:
         os.environ.pop(name, None)
     os.environ.update(env)
+    # this script times the 10 B/row binned layout (ent.dst, ent.gid);
+    # replay_compact_ab.py sets it against the compact one
+    os.environ["FUGUE_GB_REPLAY_COMPACT"] = "0"
 
 
 def _median(xs):

@@ -592,6 +592,235 @@ at::Tensor gb_replay_binned(at::Tensor vals, at::Tensor gid, at::Tensor rank,
   return out_sum;
 }
 
+// ---- compact binned dense replay: no per-row dst, 16-bit ids ----
+
+namespace {
+void scatter_tile_compact_into(const at::Tensor& vals, const at::Tensor& rank,
+                               const at::Tensor& tile_start,
+                               const at::Tensor& tile_delta, int64_t tile,
+                               int64_t threads, at::Tensor& out) {
+  check_gpu(vals, "vals");
+  check_gpu(rank, "rank");
+  check_gpu(tile_start, "tile_start");
+  check_gpu(tile_delta, "tile_delta");
+  check_tile(tile);
+  TORCH_CHECK(threads == 0 || threads == 512 || threads == 1024,
+              "threads must be 0, 512 or 1024");
+  int64_t n = rank.numel();
+  int64_t ntiles = (n + tile - 1) / tile;
+  TORCH_CHECK(vals.scalar_type() == at::kDouble && vals.numel() == n &&
+                  vals.is_contiguous(),
+              "vals must be contiguous fp64 [n]");
+  TORCH_CHECK(rank.scalar_type() == at::kShort && rank.is_contiguous(),
+              "rank must be contiguous int16 [n]");
+  TORCH_CHECK(tile_delta.scalar_type() == at::kInt && tile_delta.dim() == 2 &&
+                  tile_delta.is_contiguous() &&
+                  tile_delta.size(0) == ntiles && tile_delta.size(1) >= 1 &&
+                  tile_delta.size(1) <= SCATTER_COMPACT_MAX_BINS,
+              "tile_delta must be int32 [tiles, B], B <= ",
+              SCATTER_COMPACT_MAX_BINS);
+  int64_t nbins = tile_delta.size(1);
+  TORCH_CHECK(tile_start.scalar_type() == at::kShort &&
+                  tile_start.dim() == 2 && tile_start.is_contiguous() &&
+                  tile_start.size(0) == ntiles &&
+                  tile_start.size(1) == nbins + 1,
+              "tile_start must be int16 [tiles, B+1]");
+  if (n > 0) {
+    int err = launch_scatter_tile_compact(
+        vals.data_ptr<double>(), (const uint16_t*)rank.data_ptr<int16_t>(),
+        (const uint16_t*)tile_start.data_ptr<int16_t>(),
+        tile_delta.data_ptr<int32_t>(), (int)nbins, n, (int)tile,
+        out.data_ptr<double>(), (int)threads, current_stream());
+    TORCH_CHECK(err == 0, "scatter_tile_compact launch failed: HIP error ",
+                err);
+  }
+}
+
+void dense_aggregate_compact_into(const at::Tensor& rel,
+                                  const at::Tensor& pvals,
+                                  const at::Tensor& bin_offsets,
+                                  const at::Tensor& bin_group_base,
+                                  const at::Tensor& bin_chunk_base,
+                                  int64_t total_chunks, int64_t chunk,
+                                  int64_t slots, at::Tensor& out_sum) {
+  check_gpu(rel, "rel");
+  check_gpu(pvals, "pvals");
+  int64_t nbins = check_bins(bin_offsets);
+  check_gpu(bin_group_base, "bin_group_base");
+  check_gpu(bin_chunk_base, "bin_chunk_base");
+  check_dense_slots(slots);
+  int64_t n = rel.numel();
+  TORCH_CHECK(rel.scalar_type() == at::kShort && rel.is_contiguous(),
+              "rel must be contiguous int16");
+  TORCH_CHECK(pvals.scalar_type() == at::kDouble && pvals.numel() == n &&
+                  pvals.is_contiguous(),
+              "pvals must be contiguous fp64 [n]");
+  // the kernel reads four ids and two pairs of values per load
+  TORCH_CHECK(n == 0 ||
+                  ((uintptr_t)rel.data_ptr() % 8 == 0 &&
+                   (uintptr_t)pvals.data_ptr() % 16 == 0),
+              "rel must be 8-byte and pvals 16-byte aligned");
+  TORCH_CHECK(bin_group_base.scalar_type() == at::kLong &&
+                  bin_chunk_base.scalar_type() == at::kLong &&
+                  bin_group_base.numel() == nbins + 1 &&
+                  bin_chunk_base.numel() == nbins + 1,
+              "bin_group_base/bin_chunk_base must be int64 [B+1]");
+  TORCH_CHECK(chunk >= 1, "chunk must be >= 1");
+  TORCH_CHECK(total_chunks >= 0, "total_chunks must be >= 0");
+  if (n > 0 && total_chunks > 0) {
+    launch_gb_dense_aggregate_compact(
+        (const uint16_t*)rel.data_ptr<int16_t>(), pvals.data_ptr<double>(), n,
+        bin_offsets.data_ptr<int64_t>(), bin_group_base.data_ptr<int64_t>(),
+        bin_chunk_base.data_ptr<int64_t>(), (int)nbins, total_chunks,
+        out_sum.numel(), out_sum.data_ptr<double>(), chunk, (int)slots,
+        current_stream());
+  }
+}
+}  // namespace
+
+// scatter_tile_prepare_binned without the per-row arrays it can do
+// without: the same layout (same destination for every row), returned as
+//   rank       [n] int16 holding uint16, identical to the binned one
+//   rel        [n] int16 holding uint16, in binned order: the row's dense
+//              id less bin_group_base[its bin]
+//   tile_start [tiles, B+1] int16: first tile-local rank of every bin (the
+//              exclusive row prefix of the count matrix); the last column
+//              is the tile's placed rows, below the tile's row count only
+//              when pos is no permutation
+//   tile_delta [tiles, B] int32: destination of rank r of bin b is
+//              tile_delta[t][b] + r
+// With keep_gid a fifth tensor follows: gid [n] int32 in binned order, as
+// scatter_tile_prepare_binned returns it (for the 32-bit aggregate).
+// One host readback checks that no bin is wider than 65536 ids.
+std::vector<at::Tensor> scatter_tile_prepare_compact(
+    at::Tensor pos, at::Tensor gid, at::Tensor bin_offsets,
+    at::Tensor bin_group_base, int64_t tile, bool keep_gid) {
+  check_gpu(pos, "pos");
+  check_gpu(gid, "gid");
+  check_gpu(bin_group_base, "bin_group_base");
+  TORCH_CHECK(pos.scalar_type() == at::kInt, "pos must be int32");
+  int64_t n = pos.numel();
+  TORCH_CHECK(gid.scalar_type() == at::kInt && gid.numel() == n,
+              "gid must be int32 [n]");
+  check_tile(tile);
+  int64_t nbins = check_bins(bin_offsets);
+  TORCH_CHECK(nbins <= SCATTER_COMPACT_MAX_BINS, "at most ",
+              SCATTER_COMPACT_MAX_BINS, " bins in the compact layout");
+  TORCH_CHECK(bin_group_base.scalar_type() == at::kLong &&
+                  bin_group_base.numel() == nbins + 1,
+              "bin_group_base must be int64 [B+1]");
+  auto i16 = pos.options().dtype(at::kShort);
+  int64_t ntiles = (n + tile - 1) / tile;
+  auto rank = at::empty({n}, i16);
+  auto rel = at::empty({n}, i16);
+  at::Tensor gid_new;
+  if (keep_gid) gid_new = at::empty({n}, pos.options());
+  if (n == 0) {
+    std::vector<at::Tensor> res = {rank, rel, at::empty({0, nbins + 1}, i16),
+                                   at::empty({0, nbins}, pos.options())};
+    if (keep_gid) res.push_back(gid_new);
+    return res;
+  }
+  TORCH_CHECK((bin_group_base.slice(0, 1) - bin_group_base.slice(0, 0, nbins))
+                      .max()
+                      .item<int64_t>() <= 65536,
+              "a bin wider than 65536 ids does not fit 16-bit ids");
+  auto stream = current_stream();
+  auto counts = at::empty({ntiles, nbins}, pos.options());
+  launch_scatter_bin_count(pos.data_ptr<int32_t>(), n, (int)tile,
+                           bin_offsets.data_ptr<int64_t>(), (int)nbins,
+                           counts.data_ptr<int32_t>(), stream);
+  auto row_incl = counts.cumsum(1, at::kLong);
+  auto start = row_incl - counts;
+  // bin_offsets[b] + rows of bin b in tiles before t - start[t][b]; never
+  // below -tile, and n < 2^31 because pos is int32
+  auto tile_delta = (bin_offsets.slice(0, 0, nbins).unsqueeze(0) +
+                     (counts.cumsum(0, at::kLong) - counts) - start)
+                        .to(at::kInt)
+                        .contiguous();
+  auto tile_start = at::cat({start, row_incl.slice(1, nbins - 1, nbins)}, 1)
+                        .to(at::kShort)
+                        .contiguous();
+  launch_scatter_tile_prep_compact(
+      pos.data_ptr<int32_t>(), n, (int)tile, bin_offsets.data_ptr<int64_t>(),
+      bin_group_base.data_ptr<int64_t>(), (int)nbins,
+      tile_delta.data_ptr<int32_t>(), gid.data_ptr<int32_t>(),
+      (uint16_t*)rank.data_ptr<int16_t>(), (uint16_t*)rel.data_ptr<int16_t>(),
+      keep_gid ? gid_new.data_ptr<int32_t>() : nullptr, stream);
+  std::vector<at::Tensor> res = {rank, rel, tile_start, tile_delta};
+  if (keep_gid) res.push_back(gid_new);
+  return res;
+}
+
+// out[tile_delta[t][bin of r] + r] = value of tile t's r-th ranked row.
+// `out` (fp64 [n], contiguous) is written in place when given.
+at::Tensor scatter_tile_compact(at::Tensor vals, at::Tensor rank,
+                                at::Tensor tile_start, at::Tensor tile_delta,
+                                int64_t tile, int64_t threads,
+                                c10::optional<at::Tensor> out_opt) {
+  if (out_opt.has_value()) {
+    check_gpu(*out_opt, "out");
+    TORCH_CHECK(out_opt->scalar_type() == at::kDouble &&
+                    out_opt->is_contiguous() &&
+                    out_opt->numel() == rank.numel(),
+                "out must be contiguous fp64 [n]");
+  }
+  auto out = out_opt.has_value() ? *out_opt
+                                 : at::empty({rank.numel()}, vals.options());
+  scatter_tile_compact_into(vals, rank, tile_start, tile_delta, tile, threads,
+                            out);
+  return out;
+}
+
+// gb_dense_aggregate_binned over the 16-bit ids of the compact layout
+at::Tensor gb_dense_aggregate_compact(at::Tensor rel, at::Tensor pvals,
+                                      at::Tensor bin_offsets,
+                                      at::Tensor bin_group_base,
+                                      at::Tensor bin_chunk_base,
+                                      int64_t total_chunks, int64_t n_groups,
+                                      int64_t chunk, int64_t slots) {
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  auto out_sum = at::zeros({n_groups}, pvals.options());
+  dense_aggregate_compact_into(rel, pvals, bin_offsets, bin_group_base,
+                               bin_chunk_base, total_chunks, chunk, slots,
+                               out_sum);
+  return out_sum;
+}
+
+// One replayed step over the compact binned layout: the compact tile
+// scatter, then the aggregate `rel` selects: int16 (uint16 ids relative to
+// the bin) the 16-bit one, int32 (the binned gid) the binned one.
+at::Tensor gb_replay_compact(at::Tensor vals, at::Tensor rel, at::Tensor rank,
+                             at::Tensor tile_start, at::Tensor tile_delta,
+                             at::Tensor bin_offsets,
+                             at::Tensor bin_group_base,
+                             at::Tensor bin_chunk_base, int64_t total_chunks,
+                             int64_t n_groups, int64_t chunk, int64_t slots,
+                             int64_t tile, int64_t threads) {
+  check_gpu(vals, "vals");
+  int64_t n = rel.numel();
+  TORCH_CHECK(vals.scalar_type() == at::kDouble && vals.numel() == n,
+              "vals must be fp64 [1, n]");
+  TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
+              "n_groups must fit int32");
+  TORCH_CHECK(rank.numel() == n, "rank must be int16 [n]");
+  auto pvals = at::empty({n}, vals.options());
+  scatter_tile_compact_into(vals.view({n}), rank, tile_start, tile_delta, tile,
+                            threads, pvals);
+  auto out_sum = at::zeros({n_groups}, vals.options());
+  if (rel.scalar_type() == at::kInt) {
+    dense_aggregate_binned_into(rel, pvals, bin_offsets, bin_group_base,
+                                bin_chunk_base, total_chunks, chunk, slots,
+                                out_sum);
+  } else {
+    dense_aggregate_compact_into(rel, pvals, bin_offsets, bin_group_base,
+                                 bin_chunk_base, total_chunks, chunk, slots,
+                                 out_sum);
+  }
+  return out_sum;
+}
+
 std::vector<at::Tensor> join_build(at::Tensor keys, int64_t tsize) {
   check_gpu(keys, "keys");
   TORCH_CHECK((tsize & (tsize - 1)) == 0, "tsize must be a power of 2");
@@ -1406,6 +1635,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bin_chunk_base"), py::arg("total_chunks"),
         py::arg("n_groups"), py::arg("chunk"), py::arg("slots"),
         py::arg("tile"));
+  m.def("scatter_tile_prepare_compact", &scatter_tile_prepare_compact,
+        "compact binned preparation: rank, rel, tile_start, tile_delta",
+        py::arg("pos"), py::arg("gid"), py::arg("bin_offsets"),
+        py::arg("bin_group_base"), py::arg("tile"),
+        py::arg("keep_gid") = false);
+  m.def("scatter_tile_compact", &scatter_tile_compact,
+        "tile-coalesced value scatter over the compact binned layout",
+        py::arg("vals"), py::arg("rank"), py::arg("tile_start"),
+        py::arg("tile_delta"), py::arg("tile"), py::arg("threads") = 0,
+        py::arg("out") = py::none());
+  m.def("gb_dense_aggregate_compact", &gb_dense_aggregate_compact,
+        "sum per group over the binned layout, 16-bit ids", py::arg("rel"),
+        py::arg("pvals"), py::arg("bin_offsets"), py::arg("bin_group_base"),
+        py::arg("bin_chunk_base"), py::arg("total_chunks"),
+        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"));
+  m.def("gb_replay_compact", &gb_replay_compact,
+        "replayed step over the compact binned layout: scatter + aggregate",
+        py::arg("vals"), py::arg("rel"), py::arg("rank"),
+        py::arg("tile_start"), py::arg("tile_delta"), py::arg("bin_offsets"),
+        py::arg("bin_group_base"), py::arg("bin_chunk_base"),
+        py::arg("total_chunks"), py::arg("n_groups"), py::arg("chunk"),
+        py::arg("slots"), py::arg("tile"), py::arg("threads") = 0);
   m.def("join_build",&join_build, "build chained hash table");
   m.def("join_emit_unique", &join_emit_unique,
         "single-pass join emit for unique build keys");

@@ -27,6 +27,11 @@
 //    a bin's ids fit the LDS table), which makes the scatter's runs M //
 //    times longer (scatter_tile_prep_binned_kernel,                   //
 //    gb_dense_aggregate_binned_kernel); M = 1 is the partition layout.//
+//    The compact form of the binned layout drops the per-row           //
+//    destination for a [tiles, bins] table and keeps 16-bit ids        //
+//    relative to the bin (scatter_tile_prep_compact_kernel,            //
+//    scatter_tile_compact_kernel with a register-pipelined tile loop,  //
+//    gb_dense_aggregate_compact_kernel): 28 instead of 34 B/row moved. //
 // ------------------------------------------------------------------ //
 
 __global__ __launch_bounds__(BLOCK) void scatter_by_pos_kernel(
@@ -291,6 +296,51 @@ __global__ __launch_bounds__(BLOCK) void scatter_tile_prep_binned_kernel(
   }
 }
 
+// Compact form of the binned layout.  The destination of a tile's r-th
+// ranked row is a [tiles, bins] table plus r, and an id is a 16-bit offset
+// from its bin's first id, so neither the [n] dst nor the 32-bit gid is
+// materialised: the kernel writes rank (as scatter_tile_prep_binned_kernel
+// does) and rel[d] = gid_old[p] - bin_group_base[bin] at the destination
+// d = tile_delta[tile][bin] + r the binned kernel would have stored.  The
+// caller has checked that no bin is wider than 65536 ids.  gid_new, when
+// not null, also gets the 32-bit id in the new order.
+__global__ __launch_bounds__(BLOCK) void scatter_tile_prep_compact_kernel(
+    const int32_t* __restrict__ pos, int64_t n, int C,
+    const int64_t* __restrict__ bin_offsets,
+    const int64_t* __restrict__ bin_group_base, int nbins,
+    const int32_t* __restrict__ tile_delta,
+    const int32_t* __restrict__ gid_old, uint16_t* __restrict__ rank,
+    uint16_t* __restrict__ rel, int32_t* __restrict__ gid_new) {
+  extern __shared__ unsigned long long tile_sort[];
+  int64_t ntiles = (n + C - 1) / C;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t t0 = tile * C;
+    int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+    for (int i = threadIdx.x; i < C; i += blockDim.x) {
+      tile_sort[i] = i < cnt ? (((unsigned long long)(uint32_t)pos[t0 + i]
+                                 << 16) | (unsigned long long)i)
+                             : ~0ULL;
+    }
+    __syncthreads();
+    lds_bitonic_sort<unsigned long long>(tile_sort, C);
+    for (int r = threadIdx.x; r < cnt; r += blockDim.x) {
+      unsigned long long e = tile_sort[r];
+      int64_t p = (int64_t)(e >> 16);
+      rank[t0 + (int)(e & 0xffffULL)] = (uint16_t)r;
+      if (p < n) {
+        int b = bin_of(bin_offsets, nbins, p);
+        int64_t d = (int64_t)tile_delta[tile * nbins + b] + r;
+        if ((uint64_t)d < (uint64_t)n) {
+          int32_t g = gid_old[p];
+          rel[d] = (uint16_t)((int64_t)g - bin_group_base[b]);
+          if (gid_new != nullptr) gid_new[d] = g;  // for the 32-bit aggregate
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // ------------------------------------------------------------------ //
 // dense replay: per-step kernels                                      //
 // ------------------------------------------------------------------ //
@@ -341,6 +391,101 @@ __global__ __launch_bounds__(BLOCK) void scatter_tile_kernel(
     for (; i < cnt; i += stride) {
       int64_t d = td[i];
       if ((uint64_t)d < (uint64_t)n) out[d] = tile_vals[i];
+    }
+    __syncthreads();
+  }
+}
+
+// scatter_tile_kernel over the compact binned layout.  tile_start is
+// [tiles, bins + 1] (first tile-local rank of every bin, then the tile's
+// placed rows), tile_delta [tiles, bins]; both rows of the tile sit in LDS
+// behind the value tile (768 B at 128 bins).  A wave stores a contiguous
+// span of ranks, 64 at a time: each lane searches its first rank's bin
+// once and then only walks forward, because its ranks ascend.  Ranks at or
+// past the tile's placed rows (positions that were no permutation) are
+// dropped, and the parent's bound check on the destination stays.
+//
+// The loop over tiles is software-pipelined: the next tile's values and
+// ranks are loaded into registers before the current tile is stored, so
+// the loads are in flight during the store phase.  NT threads hold
+// 8192 / NT rows each.
+template <int NT>
+__global__ __launch_bounds__(NT, NT / 128) void scatter_tile_compact_kernel(
+    const double* __restrict__ vals, const uint16_t* __restrict__ rank,
+    const uint16_t* __restrict__ tile_start,
+    const int32_t* __restrict__ tile_delta, int nbins, int64_t n, int C,
+    double* __restrict__ out) {
+  constexpr int R = 8192 / NT;  // value rows per thread
+  // table entries per thread: SCATTER_COMPACT_MAX_BINS + 1 over NT threads
+  constexpr int TB = (SCATTER_COMPACT_MAX_BINS + NT) / NT;
+  extern __shared__ double tile_vals[];
+  int32_t* td = (int32_t*)(tile_vals + C);
+  uint16_t* ts = (uint16_t*)(td + nbins);
+  const int64_t ntiles = (n + C - 1) / C;
+  const int tid = threadIdx.x;
+  // rows per thread at this tile size, and this lane's first rank
+  const int rc = C >= NT ? C / NT : 1;
+  const int i0 = (tid >> 6) * (rc << 6) + (tid & 63);
+  double v[R];
+  unsigned r[R], ps[TB];
+  int pd[TB];
+  // Loads of one tile into registers, nothing else: every load is
+  // unconditional off a scalar base (an index past the end is clamped and
+  // the row dropped when the registers are consumed), so no instruction
+  // after the loads has to wait for them.
+  auto load_tile = [&](int64_t t) {
+    const int64_t t0 = t * C;
+    const int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+    const double* tv = vals + t0;
+    const uint16_t* tr = rank + t0;
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      int i = tid + u * NT;
+      unsigned ii = (unsigned)(i < cnt ? i : cnt - 1);
+      v[u] = tv[ii];
+      r[u] = tr[ii];
+    }
+    const int32_t* gd = tile_delta + t * nbins;
+    const uint16_t* gs = tile_start + t * (nbins + 1);
+#pragma unroll
+    for (int k = 0; k < TB; ++k) {
+      int b = tid + k * NT;
+      pd[k] = gd[(unsigned)(b < nbins ? b : nbins - 1)];
+      ps[k] = gs[(unsigned)(b < nbins ? b : nbins)];
+    }
+  };
+  int64_t tile = blockIdx.x;
+  if (tile < ntiles) load_tile(tile);
+  for (; tile < ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * C;
+    const int cnt = (int)((n - t0) < (int64_t)C ? (n - t0) : (int64_t)C);
+#pragma unroll
+    for (int u = 0; u < R; ++u)
+      if (tid + u * NT < cnt && r[u] < (unsigned)cnt) tile_vals[r[u]] = v[u];
+#pragma unroll
+    for (int k = 0; k < TB; ++k) {
+      int b = tid + k * NT;
+      if (b < nbins) td[b] = pd[k];
+      if (b <= nbins) ts[b] = (uint16_t)ps[k];
+    }
+    __syncthreads();
+    const int64_t next = tile + gridDim.x;
+    if (next < ntiles) load_tile(next);  // in flight during the stores
+    int lim = (int)ts[nbins];
+    if (lim > cnt) lim = cnt;
+    if (i0 < lim) {
+      int b = 0, hi = nbins;  // largest b with ts[b] <= i0 (ts[0] == 0)
+      while (hi - b > 1) {
+        int mid = (b + hi) >> 1;
+        if ((int)ts[mid] <= i0) b = mid; else hi = mid;
+      }
+      // not unrolled: the registers belong to the next tile's rows
+#pragma unroll 1
+      for (int i = i0, e = i0 + (rc << 6); i < e && i < lim; i += 64) {
+        while (b + 1 < nbins && (int)ts[b + 1] <= i) ++b;
+        int64_t d = (int64_t)td[b] + i;
+        if ((uint64_t)d < (uint64_t)n) out[d] = tile_vals[i];
+      }
     }
     __syncthreads();
   }
@@ -486,6 +631,89 @@ __global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_binned_kernel(
   }
 }
 
+// gb_dense_aggregate_binned_kernel over 16-bit ids: rel[j] is the id of
+// row j less its bin's first id, so the table index needs no subtraction
+// and a row costs 10 bytes instead of 12.  A rel past the table (a bin
+// wider than SLOTS) adds straight to out_sum[base + rel], as there.  rel
+// and part_vals are 16-byte aligned at row 0 (whole allocations).
+template <int SLOTS>
+__global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_compact_kernel(
+    const uint16_t* __restrict__ rel, const double* __restrict__ part_vals,
+    int64_t n, const int64_t* __restrict__ bin_offsets,
+    const int64_t* __restrict__ bin_group_base,
+    const int64_t* __restrict__ bin_chunk_base, int nbins,
+    int64_t total_chunks, int64_t n_groups, double* __restrict__ out_sum,
+    int64_t chunk) {
+  __shared__ double lsum[SLOTS];
+  for (int64_t vc = blockIdx.x; vc < total_chunks; vc += gridDim.x) {
+    for (int i = threadIdx.x; i < SLOTS; i += blockDim.x) lsum[i] = 0.0;
+    const int b = bin_of(bin_chunk_base, nbins, vc);
+    int64_t start = bin_offsets[b] + (vc - bin_chunk_base[b]) * chunk;
+    int64_t end = start + chunk;
+    const int64_t bin_end = bin_offsets[b + 1];
+    if (end > bin_end) end = bin_end;
+    // rows read stay inside [0, n) whatever the bin arrays hold
+    if (start < 0) start = 0;
+    if (end > n) end = n;
+    const int64_t base = bin_group_base[b];
+    __syncthreads();
+    auto add = [&](unsigned g, double v) {
+      if (g < (unsigned)SLOTS) {
+        atomicAdd(&lsum[g], v);
+      } else if ((uint64_t)(base + g) < (uint64_t)n_groups) {
+        atomicAdd(&out_sum[base + g], v);
+      }
+    };
+    // A lane takes four consecutive rows: their ids are one 8-byte load
+    // (2-byte loads per lane were slower than the 32-bit ids they replace)
+    // and their values two 16-byte loads.  Rows before the first multiple
+    // of four and after the last go one per lane.
+    int64_t a0 = (start + 3) & ~(int64_t)3;
+    if (a0 > end) a0 = end;
+    const int64_t a1 = a0 + ((end - a0) & ~(int64_t)3);
+    {
+      int64_t h = start + threadIdx.x;
+      if (h < a0) add(rel[h], part_vals[h]);
+      int64_t t = a1 + threadIdx.x;
+      if (t < end) add(rel[t], part_vals[t]);
+    }
+    const int64_t stride = (int64_t)blockDim.x * 4;
+    int64_t i = a0 + (int64_t)threadIdx.x * 4;
+    for (; i + stride < a1; i += 2 * stride) {
+      uint2 g0 = *(const uint2*)(rel + i);
+      uint2 g1 = *(const uint2*)(rel + i + stride);
+      double2 v0 = *(const double2*)(part_vals + i);
+      double2 v1 = *(const double2*)(part_vals + i + 2);
+      double2 v2 = *(const double2*)(part_vals + i + stride);
+      double2 v3 = *(const double2*)(part_vals + i + stride + 2);
+      add(g0.x & 0xffffu, v0.x);
+      add(g0.x >> 16, v0.y);
+      add(g0.y & 0xffffu, v1.x);
+      add(g0.y >> 16, v1.y);
+      add(g1.x & 0xffffu, v2.x);
+      add(g1.x >> 16, v2.y);
+      add(g1.y & 0xffffu, v3.x);
+      add(g1.y >> 16, v3.y);
+    }
+    if (i < a1) {
+      uint2 g0 = *(const uint2*)(rel + i);
+      double2 v0 = *(const double2*)(part_vals + i);
+      double2 v1 = *(const double2*)(part_vals + i + 2);
+      add(g0.x & 0xffffu, v0.x);
+      add(g0.x >> 16, v0.y);
+      add(g0.y & 0xffffu, v1.x);
+      add(g0.y >> 16, v1.y);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < SLOTS; s += blockDim.x) {
+      double v = lsum[s];
+      if (v != 0.0 && (uint64_t)(base + s) < (uint64_t)n_groups)
+        atomicAdd(&out_sum[base + s], v);
+    }
+    __syncthreads();
+  }
+}
+
 extern "C" {
 
 void launch_gb_dense_count(const int64_t* pkeys, const int64_t* offsets,
@@ -598,6 +826,102 @@ void launch_gb_dense_aggregate_binned(
     default:
       hipLaunchKernelGGL((gb_dense_aggregate_binned_kernel<8192>), g, b, 0,
                          stream, gid, part_vals, n, bin_offsets,
+                         bin_group_base, bin_chunk_base, nbins, total_chunks,
+                         n_groups, out_sum, chunk);
+  }
+}
+
+// ---- compact binned layout ----
+
+void launch_scatter_tile_prep_compact(
+    const int32_t* pos, int64_t n, int tile, const int64_t* bin_offsets,
+    const int64_t* bin_group_base, int nbins, const int32_t* tile_delta,
+    const int32_t* gid_old, uint16_t* rank, uint16_t* rel, int32_t* gid_new,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_tile_prep_compact_kernel,
+                     dim3(chunk_grid(n, tile)), dim3(BLOCK),
+                     (size_t)tile * sizeof(unsigned long long), stream, pos, n,
+                     tile, bin_offsets, bin_group_base, nbins, tile_delta,
+                     gid_old, rank, rel, gid_new);
+}
+
+}  // extern "C"
+
+namespace {
+template <int NT>
+hipError_t scatter_tile_compact_launch(
+    const double* vals, const uint16_t* rank, const uint16_t* tile_start,
+    const int32_t* tile_delta, int nbins, int64_t n, int tile, double* out,
+    hipStream_t stream) {
+  // value tile, then the tile's delta and start rows; past 64KB the block
+  // opts in to the large LDS of CDNA4 (160KB per CU)
+  size_t lds = (size_t)tile * sizeof(double) + (size_t)nbins * 4 +
+               (((size_t)nbins + 1) * 2 + 7) / 8 * 8;
+  if (lds > 65536) {
+    // once per device and instantiation, for the most the kernel asks for
+    static bool opted[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !opted[dev]) {
+      e = hipFuncSetAttribute(
+          reinterpret_cast<const void*>(&scatter_tile_compact_kernel<NT>),
+          hipFuncAttributeMaxDynamicSharedMemorySize,
+          8192 * 8 + SCATTER_COMPACT_MAX_BINS * 4 +
+              (SCATTER_COMPACT_MAX_BINS + 8) * 2);
+      if (e != hipSuccess) return e;
+      if (dev >= 0 && dev < 64) opted[dev] = true;
+    }
+  }
+  hipLaunchKernelGGL((scatter_tile_compact_kernel<NT>),
+                     dim3(chunk_grid(n, tile)), dim3(NT), lds, stream, vals,
+                     rank, tile_start, tile_delta, nbins, n, tile, out);
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+// nbins <= SCATTER_COMPACT_MAX_BINS; threads is 512 or 1024 (0: the
+// default).  Returns the HIP error of the launch.
+int launch_scatter_tile_compact(const double* vals, const uint16_t* rank,
+                                const uint16_t* tile_start,
+                                const int32_t* tile_delta, int nbins,
+                                int64_t n, int tile, double* out, int threads,
+                                hipStream_t stream) {
+  switch (threads) {
+    case 512:
+      return (int)scatter_tile_compact_launch<512>(
+          vals, rank, tile_start, tile_delta, nbins, n, tile, out, stream);
+    default:
+      return (int)scatter_tile_compact_launch<1024>(
+          vals, rank, tile_start, tile_delta, nbins, n, tile, out, stream);
+  }
+}
+
+void launch_gb_dense_aggregate_compact(
+    const uint16_t* rel, const double* part_vals, int64_t n,
+    const int64_t* bin_offsets, const int64_t* bin_group_base,
+    const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
+    int64_t n_groups, double* out_sum, int64_t chunk, int slots,
+    hipStream_t stream) {
+  dim3 g(chunk_grid(total_chunks, 1)), b(BLOCK);
+  switch (slots) {
+    case 2048:
+      hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<2048>), g, b, 0,
+                         stream, rel, part_vals, n, bin_offsets,
+                         bin_group_base, bin_chunk_base, nbins, total_chunks,
+                         n_groups, out_sum, chunk);
+      break;
+    case 4096:
+      hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<4096>), g, b, 0,
+                         stream, rel, part_vals, n, bin_offsets,
+                         bin_group_base, bin_chunk_base, nbins, total_chunks,
+                         n_groups, out_sum, chunk);
+      break;
+    default:
+      hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<8192>), g, b, 0,
+                         stream, rel, part_vals, n, bin_offsets,
                          bin_group_base, bin_chunk_base, nbins, total_chunks,
                          n_groups, out_sum, chunk);
   }

@@ -27,6 +27,9 @@
 #define DENSE_ASSIGN_MAX 2048
 // binned dense replay: most bins (LDS histogram of the bin count kernel)
 #define BIN_MAX 4096
+// compact binned replay: most bins (two table rows of the tile sit in LDS
+// behind the 64KB value tile)
+#define SCATTER_COMPACT_MAX_BINS 512
 
 // group-by key preparation: most key columns per pack / key-stats launch
 #define PACK_MAX_COLS 8
@@ -169,6 +172,22 @@ void launch_scatter_tile_prep_binned(const int32_t* pos, int64_t n, int tile,
                                      hipStream_t stream);
 void launch_gb_dense_aggregate_binned(
     const int32_t* gid, const double* part_vals, int64_t n,
+    const int64_t* bin_offsets, const int64_t* bin_group_base,
+    const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
+    int64_t n_groups, double* out_sum, int64_t chunk, int slots,
+    hipStream_t stream);
+void launch_scatter_tile_prep_compact(
+    const int32_t* pos, int64_t n, int tile, const int64_t* bin_offsets,
+    const int64_t* bin_group_base, int nbins, const int32_t* tile_delta,
+    const int32_t* gid_old, uint16_t* rank, uint16_t* rel, int32_t* gid_new,
+    hipStream_t stream);
+int launch_scatter_tile_compact(const double* vals, const uint16_t* rank,
+                                const uint16_t* tile_start,
+                                const int32_t* tile_delta, int nbins,
+                                int64_t n, int tile, double* out, int threads,
+                                hipStream_t stream);
+void launch_gb_dense_aggregate_compact(
+    const uint16_t* rel, const double* part_vals, int64_t n,
     const int64_t* bin_offsets, const int64_t* bin_group_base,
     const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
     int64_t n_groups, double* out_sum, int64_t chunk, int slots,

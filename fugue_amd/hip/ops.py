@@ -231,9 +231,14 @@ _KEY_STATS_MEMO_CAP = 128
 # null-free fp64 column, FUGUE_GB_REPLAY_DENSE=1) caches per row the
 # dense group id (4 B) and the tile scatter's rank + destination
 # (2 B + 4 B) = 10 B/row, plus keys and counts per GROUP; pkeys and pos
-# are dropped (the same 10 B/row when the values are laid out by bins
-# of partitions, FUGUE_GB_REPLAY_BIN_PARTS).  Two entries ~1.25GB each
-# at 125M rows — bound the cache tightly.
+# are dropped.  When the values are laid out by bins of partitions
+# (FUGUE_GB_REPLAY_BIN_PARTS) the compact form (FUGUE_GB_REPLAY_COMPACT)
+# keeps the rank and a 16-bit id relative to the bin (2 B + 2 B) = 4
+# B/row plus a [tiles, bins] destination table (6 B per tile and bin,
+# under 12 MB at 125M rows); with the knob off, or more than tile/16
+# bins, the binned layout keeps the 10 B/row.  Two entries ~0.5GB each
+# at 125M rows (~1.25GB each when not compact) — bound the cache
+# tightly.
 _LAYOUT_MEMO: "Dict[Tuple[Any, ...], Any]" = {}
 _LAYOUT_MEMO_CAP = 2
 # key tensors seen once (candidates): recording uses the slower simple
@@ -327,10 +332,14 @@ class _DenseLayout:
     0: ``pos``).  With ``bin_parts`` > 1 the values are laid out by bins
     of that many consecutive hash partitions instead (``rank``, ``dst``
     and ``gid`` from ``scatter_tile_prepare_binned``; ``gid`` is then in
-    binned order) and the bin arrays drive the aggregate."""
+    binned order) and the bin arrays drive the aggregate.  A compact
+    binned entry (``tile_start`` is not None, from
+    ``scatter_tile_prepare_compact``) holds the per-tile tables instead of
+    ``dst``, and either the 16-bit ``rel`` (``gid`` is None) or, with
+    ``FUGUE_GB_REPLAY_COMPACT=2``, the int32 ``gid`` (``rel`` is None)."""
 
     ref: Any
-    gid: "torch.Tensor"
+    gid: Optional["torch.Tensor"]
     offsets: "torch.Tensor"
     group_base: "torch.Tensor"
     n_groups: int
@@ -348,6 +357,9 @@ class _DenseLayout:
     bin_chunks: int = 0  # total aggregate chunks over all bins
     bin_chunk: int = 0  # rows per aggregate chunk bin_chunk_base is for
     bin_slots: int = 0  # table slots the bin width was chosen for
+    rel: Optional["torch.Tensor"] = None  # [n] uint16 id - bin_group_base
+    tile_start: Optional["torch.Tensor"] = None  # [tiles, B+1] uint16
+    tile_delta: Optional["torch.Tensor"] = None  # [tiles, B] int32
 
 
 def _layout_get(lkey: tuple) -> Any:
@@ -385,6 +397,7 @@ def _prepare_dense_layout(
     ext: Any, packed: "torch.Tensor", pkeys: "torch.Tensor",
     pos: "torch.Tensor", num_parts: int, tile: int,
     bin_parts: int = 1, bin_slots: int = 8192, bin_chunk: int = 65536,
+    compact: int = 0,
 ) -> Optional[_DenseLayout]:
     """One-time preparation of the dense replay layout from the recorded
     partitioned keys (int64) and per-row spill positions; None when it is
@@ -392,7 +405,11 @@ def _prepare_dense_layout(
     table, or G >= 2^31) and the plain replay entry must be kept.  One
     host readback, once per key tensor.  ``bin_parts`` is the most
     partitions a bin of the value layout may hold (1: keep the partition
-    layout); the width used is the widest whose bins fit ``bin_slots``."""
+    layout); the width used is the widest whose bins fit ``bin_slots``.
+    ``compact`` asks for the compact form of a binned layout, taken when
+    its per-tile table is at most 1/8 of the ``dst`` bytes it replaces
+    (``nbins <= tile // 16``): 1 with 16-bit ids, 2 with the int32 ids
+    and the binned aggregate."""
     offsets, distinct = ext.gb_dense_count(pkeys=pkeys, num_parts=num_parts)
     group_base = torch.zeros(
         num_parts + 1, dtype=torch.int64, device=pkeys.device
@@ -432,18 +449,32 @@ def _prepare_dense_layout(
         )
         bin_chunk_base = torch.zeros(chunks.numel() + 1, dtype=torch.int64)
         torch.cumsum(chunks, 0, out=bin_chunk_base[1:])
-        rank, dst, gid = ext.scatter_tile_prepare_binned(
-            pos=pos, gid=gid, bin_offsets=bin_offsets, tile=tile
-        )
+        bin_group_base = group_base[::m].contiguous()
+        dst = rel = tile_start = tile_delta = None
+        if compact and num_parts // m <= tile // 16:
+            out = ext.scatter_tile_prepare_compact(
+                pos=pos, gid=gid, bin_offsets=bin_offsets,
+                bin_group_base=bin_group_base, tile=tile,
+                keep_gid=compact == 2,
+            )
+            rank, rel, tile_start, tile_delta = out[:4]
+            gid = None
+            if compact == 2:
+                gid, rel = out[4], None
+        else:
+            rank, dst, gid = ext.scatter_tile_prepare_binned(
+                pos=pos, gid=gid, bin_offsets=bin_offsets, tile=tile
+            )
         return _DenseLayout(
             ref=weakref.ref(packed), gid=gid, offsets=offsets,
             group_base=group_base, n_groups=int(n_groups),
             out_keys=out_keys, out_count=out_count, rank=rank, dst=dst,
             pos=None, tile=tile, bin_parts=m, bin_offsets=bin_offsets,
-            bin_group_base=group_base[::m].contiguous(),
+            bin_group_base=bin_group_base,
             bin_chunk_base=bin_chunk_base.to(pkeys.device),
             bin_chunks=int(bin_chunk_base[-1]), bin_chunk=bin_chunk,
-            bin_slots=bin_slots,
+            bin_slots=bin_slots, rel=rel, tile_start=tile_start,
+            tile_delta=tile_delta,
         )
     rank = dst = None
     if tile > 0:
@@ -489,6 +520,11 @@ class _GbKnobs:
     # 4096 or 8192) and rows per chunk of the binned dense aggregate
     bin_slots: int = 8192
     bin_chunk: int = 65536
+    # FUGUE_GB_REPLAY_COMPACT: a binned layout with at most tile/16 bins
+    # keeps no per-row destination and 16-bit ids (0: the 10 B/row
+    # binned layout, kept for A/B; 2: no destination but the int32 ids
+    # and the binned aggregate, 8 B/row, kept for A/B)
+    replay_compact: int = 1
 
     @classmethod
     def from_env(cls) -> "_GbKnobs":
@@ -509,6 +545,7 @@ class _GbKnobs:
             )
         bin_slots = int(env("FUGUE_GB_BIN_SLOTS", "8192"))
         bin_chunk = int(env("FUGUE_GB_BIN_CHUNK", "65536"))
+        compact = int(env("FUGUE_GB_REPLAY_COMPACT", "1"))
         return cls(
             staged_max=int(env("FUGUE_GB_STAGED_MAX", "1200000")),
             parts=parts if parts in (512, 1024, 2048) else 512,
@@ -523,6 +560,9 @@ class _GbKnobs:
             replay_bin_parts=bin_parts,
             bin_slots=bin_slots if bin_slots in (2048, 4096, 8192) else 8192,
             bin_chunk=bin_chunk if bin_chunk >= 256 else 65536,
+            replay_compact=(
+                compact if compact in (0, 1, 2) else 1
+            ),
         )
 
 
@@ -1023,9 +1063,10 @@ def groupby_aggregate(
         # the dense gate and the scatter tile are part of the memo key so
         # an in-process A/B keeps one entry per side
         # the bin knobs shape the dense layout (tile scatter only)
-        bins = (1, 0, 0)
+        bins = (1, 0, 0, 0)
         if plan.dense_ok and plan.tile > 0 and knobs.replay_bin_parts > 1:
-            bins = (knobs.replay_bin_parts, knobs.bin_slots, knobs.bin_chunk)
+            bins = (knobs.replay_bin_parts, knobs.bin_slots, knobs.bin_chunk,
+                    knobs.replay_compact)
         lkey = (
             packed.data_ptr(), n, plan.num_parts, plan.tsize, plan.narrow,
             plan.dense_ok, plan.tile,
@@ -1039,7 +1080,19 @@ def groupby_aggregate(
             # purpose: columns are immutable, and a stable key tensor
             # lets the identity-memoized key stats of a downstream join
             # hit instead of re-running.
-            if ent.bin_parts > 1:
+            if ent.tile_start is not None:
+                out_sum = ext.gb_replay_compact(
+                    vals=vals,
+                    rel=ent.rel if ent.rel is not None else ent.gid,
+                    rank=ent.rank,
+                    tile_start=ent.tile_start, tile_delta=ent.tile_delta,
+                    bin_offsets=ent.bin_offsets,
+                    bin_group_base=ent.bin_group_base,
+                    bin_chunk_base=ent.bin_chunk_base,
+                    total_chunks=ent.bin_chunks, n_groups=ent.n_groups,
+                    chunk=ent.bin_chunk, slots=ent.bin_slots, tile=ent.tile,
+                )
+            elif ent.bin_parts > 1:
                 out_sum = ext.gb_replay_binned(
                     vals=vals, gid=ent.gid, rank=ent.rank, dst=ent.dst,
                     bin_offsets=ent.bin_offsets,
