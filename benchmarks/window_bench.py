@@ -14,6 +14,14 @@ per shape.
     python benchmarks/window_bench.py [--rows 1000000,4000000]
         [--groups 1000,1000000] [--steps 5] [--host-steps 3] [--warmup 2]
 
+``--partition`` runs the whole-partition case instead: percent-of-total
+plus ``FIRST_VALUE`` (``engine.partition_over``, the ``seg_total_*``
+kernels) against the same forced host path, and times the
+``segmented_total`` launch chain alone with device events next to a plain
+copy of the bytes it moves at the least (120 B/row: 24 for the forward
+summary, 40 for the forward apply, 8 for the backward summary, 48 for the
+backward apply).
+
 ``--kernels N`` instead runs only the kernels (and a plain copy of the
 bytes they move at the least: 33 B/row for the shift, 24 + 40 B/row for
 the scan's summary and apply) N times on the first shape, for a
@@ -43,7 +51,15 @@ _SQL = (
 )
 
 
-def _step(engine, hdf, host: bool):
+_PARTITION_SQL = (
+    "SELECT k, v, v / t AS share, f FROM (SELECT k, v, "
+    "SUM(v) OVER (PARTITION BY k) AS t, "
+    "FIRST_VALUE(v) OVER (PARTITION BY k) AS f FROM df)"
+)
+_TOTAL_BYTES_PER_ROW = 120
+
+
+def _step(engine, hdf, host: bool, sql: str = _SQL):
     if host:
         os.environ[_FORCE_HOST] = "1"
     else:
@@ -51,7 +67,7 @@ def _step(engine, hdf, host: bool):
     try:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        res = fugue_sql(_SQL, df=hdf, engine=engine, as_fugue=True)
+        res = fugue_sql(sql, df=hdf, engine=engine, as_fugue=True)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3, res
     finally:
@@ -105,6 +121,81 @@ def _kernels_only(engine, hdf, reps: int) -> None:
                           copy_elems={str(b): int(t.numel()) for b, t in src.items()})))
 
 
+def _event_ms(fn, reps: int) -> float:
+    """Median device time of one call of ``fn`` (device events)."""
+    out = []
+    for _ in range(reps):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+def _partition_digest(res) -> tuple:
+    pdf = res.as_pandas()
+    return (
+        len(pdf), int(pdf["k"].sum()), float(pdf["share"].sum()),
+        int(pdf["share"].isna().sum()), float(pdf["f"].sum()),
+    )
+
+
+def _partition_case(engine, args, n: int, g: int) -> None:
+    hdf = _frame(engine, n, g)
+    before = engine.stats.get("window.device_partition")
+    for _ in range(args.warmup):
+        _, dres = _step(engine, hdf, False, _PARTITION_SQL)
+    _, hres = _step(engine, hdf, True, _PARTITION_SQL)
+    assert engine.stats.get("window.device_partition") == before + 2 * args.warmup
+    same = _partition_digest(dres) == _partition_digest(hres)
+    dev_ms, host_ms = [], []
+    for i in range(max(args.steps, args.host_steps)):
+        if i < args.steps:
+            dev_ms.append(_step(engine, hdf, False, _PARTITION_SQL)[0])
+        if i < args.host_steps:
+            host_ms.append(_step(engine, hdf, True, _PARTITION_SQL)[0])
+    pkeys, perm = engine._partition_sort(hdf, ["k"], [], [], "last")
+    c = hdf.col("v")
+    src = torch.empty(
+        n * _TOTAL_BYTES_PER_ROW // 16, dtype=torch.int64, device=perm.device
+    )
+    for _ in range(3):
+        dops.segmented_total(perm, pkeys, c, "sum")
+        src.clone()
+    total_ms = _event_ms(lambda: dops.segmented_total(perm, pkeys, c, "sum"), 20)
+    copy_ms = _event_ms(lambda: src.clone(), 20)
+    d, h = float(np.median(dev_ms)), float(np.median(host_ms))
+    nbytes = n * _TOTAL_BYTES_PER_ROW
+    print(
+        json.dumps(
+            dict(
+                bench="window_partition_share_first",
+                rows=n,
+                groups=g,
+                device_ms=round(d, 3),
+                device_ms_min=round(min(dev_ms), 3),
+                device_ms_max=round(max(dev_ms), 3),
+                host_ms=round(h, 3),
+                host_ms_min=round(min(host_ms), 3),
+                host_ms_max=round(max(host_ms), 3),
+                host_over_device=round(h / d, 2),
+                results_equal=bool(same),
+                seg_total_ms=round(total_ms, 4),
+                seg_total_gbps=round(nbytes / total_ms / 1e6, 1),
+                copy_ms=round(copy_ms, 4),
+                copy_gbps=round(nbytes / copy_ms / 1e6, 1),
+                steps=args.steps,
+                host_steps=args.host_steps,
+                warmup=args.warmup,
+            )
+        ),
+        flush=True,
+    )
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="1000000,4000000,16000000")
@@ -113,6 +204,7 @@ def main() -> None:
     ap.add_argument("--host-steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kernels", type=int, default=0)
+    ap.add_argument("--partition", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("window_bench needs a GPU")
@@ -121,6 +213,11 @@ def main() -> None:
     groups = [int(x) for x in args.groups.split(",")]
     if args.kernels > 0:
         _kernels_only(engine, _frame(engine, rows[0], groups[0]), args.kernels)
+        return
+    if args.partition:
+        for n in rows:
+            for g in groups:
+                _partition_case(engine, args, n, g)
         return
     for n in rows:
         for g in groups:

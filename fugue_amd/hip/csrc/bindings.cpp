@@ -1573,6 +1573,31 @@ std::vector<at::Tensor> seg_scan(at::Tensor perm, at::Tensor pkeys,
   return {acc, cnt};
 }
 
+// Whole-partition SUM (op 0) / MIN (1) / MAX (2) / FIRST (3) / LAST (4)
+// of the non-null values, and their count, given to every row of the
+// partition.  Returns (acc in the input dtype, cnt int64) in original
+// row order.
+std::vector<at::Tensor> seg_total(at::Tensor perm, at::Tensor pkeys,
+                                  at::Tensor data,
+                                  c10::optional<at::Tensor> valid,
+                                  int64_t op) {
+  seg_check_inputs(perm, pkeys);
+  int64_t n = perm.numel();
+  const uint8_t* vp = seg_check_value(data, valid, n);
+  TORCH_CHECK(op >= 0 && op <= 4, "op must be 0..4");
+  auto acc = at::empty_like(data);
+  auto cnt = at::empty({n}, perm.options());
+  if (n == 0) return {acc, cnt};
+  auto work = at::empty({SEG_TOTAL_WORK(n)}, perm.options());
+  launch_seg_total(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(),
+                   reinterpret_cast<const int64_t*>(data.data_ptr()), vp, n,
+                   (int)op, data.is_floating_point() ? 1 : 0,
+                   work.data_ptr<int64_t>(),
+                   reinterpret_cast<int64_t*>(acc.data_ptr()),
+                   cnt.data_ptr<int64_t>(), current_stream());
+  return {acc, cnt};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // limits the python layer plans by (ops.py keeps copies for hosts
   // without the extension; a GPU test compares them)
@@ -1685,6 +1710,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "segment-bounded shift (LAG/LEAD) in original row order");
   m.def("seg_scan", &seg_scan,
         "segmented running sum/min/max + non-null count");
+  m.def("seg_total", &seg_total,
+        "whole-partition sum/min/max/first/last + non-null count");
   m.def("gb_compact", &gb_compact,
         "deterministic group-table compaction");
   m.def("compact_columns_cap", &compact_columns_cap,

@@ -59,6 +59,10 @@ struct ExprProg {
 // segmented rank: sorted positions per block, most order columns
 #define SEG_CHUNK (BLOCK * 32)
 #define SEG_MAX_COLS 4
+// seg_total work buffer in int64 words: 8 per chunk (chunk aggregates and
+// carries of both passes), then the forward (acc, cnt) of every position
+#define SEG_TOTAL_WORK(n) \
+  (8 * (((int64_t)(n) + SEG_CHUNK - 1) / SEG_CHUNK) + 2 * (int64_t)(n))
 
 // top-k select: largest k, most stage-1 blocks (candidate rows = blocks * k)
 #define TOPK_MAX 16
@@ -283,5 +287,10 @@ void launch_seg_scan(const int64_t* perm, const int64_t* pkeys,
                      const int64_t* vals, const uint8_t* valid, int64_t n,
                      int op, int is_float, int64_t* work, int64_t* out_acc,
                      int64_t* out_cnt, hipStream_t stream);
+// op 0..2 as launch_seg_scan, 3 FIRST, 4 LAST; work: SEG_TOTAL_WORK(n)
+void launch_seg_total(const int64_t* perm, const int64_t* pkeys,
+                      const int64_t* vals, const uint8_t* valid, int64_t n,
+                      int op, int is_float, int64_t* work, int64_t* out_acc,
+                      int64_t* out_cnt, hipStream_t stream);
 
 }  // extern "C"

@@ -526,6 +526,13 @@ __global__ __launch_bounds__(BLOCK) void seg_shift_kernel(
 #define SEG_OP_SUM 0
 #define SEG_OP_MIN 1
 #define SEG_OP_MAX 2
+// seg_total only: the first / last non-null value in sorted order
+#define SEG_OP_FIRST 3
+#define SEG_OP_LAST 4
+
+// sign bit of a count in seg_total's scratch: the position starts a
+// partition
+#define SEG_HEAD_BIT ((int64_t)0x8000000000000000LL)
 
 // Scan element of a range of sorted positions: head says the range holds
 // a partition start, and then acc/cnt cover the positions from the LAST
@@ -550,6 +557,8 @@ __device__ __forceinline__ SegVal seg_val_identity() {
 // NaN never arrives here (the caller passes it as null).
 __device__ __forceinline__ int64_t seg_val_op(int64_t a, int64_t b, int op,
                                               int is_float) {
+  if (op == SEG_OP_FIRST) return a;
+  if (op == SEG_OP_LAST) return b;
   if (is_float) {
     double x = __longlong_as_double(a), y = __longlong_as_double(b);
     double r = op == SEG_OP_SUM ? x + y
@@ -695,15 +704,19 @@ __global__ __launch_bounds__(BLOCK) void seg_scan_scan_kernel(
   }
 }
 
-// writes acc and cnt of every row, null rows included (they carry the
-// running value through; acc is 0 while cnt is 0)
-__global__ __launch_bounds__(BLOCK) void seg_scan_apply_kernel(
+// The apply step of the scan.  SORTED = false writes acc and cnt of every
+// row, null rows included (they carry the running value through; acc is
+// 0 while cnt is 0), to out[perm[i]].  SORTED = true is the forward pass
+// of seg_total: the same values land coalesced at out[i], and the sign
+// bit of out_cnt[i] marks a partition start (cnt is never negative).
+template <bool SORTED>
+__device__ __forceinline__ void seg_scan_apply(
     const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
     const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
     int64_t n, int op, int is_float, const int64_t* __restrict__ car_head,
     const int64_t* __restrict__ car_acc, const int64_t* __restrict__ car_cnt,
-    int64_t* __restrict__ out_acc, int64_t* __restrict__ out_cnt) {
-  __shared__ SegVal ws[2][SEG_WAVES];
+    int64_t* __restrict__ out_acc, int64_t* __restrict__ out_cnt,
+    SegVal (*ws)[SEG_WAVES]) {
   int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
   int lane = threadIdx.x % WAVE;
   int wave = threadIdx.x / WAVE;
@@ -722,8 +735,151 @@ __global__ __launch_bounds__(BLOCK) void seg_scan_apply_kernel(
     SegVal r =
         seg_val_block_step(x, lane, wave, op, is_float, carry, ws[it & 1]);
     if (i < n) {
-      out_acc[j] = r.acc;
-      out_cnt[j] = r.cnt;
+      if (SORTED) {
+        out_acc[i] = r.acc;
+        out_cnt[i] = x.head ? (r.cnt | SEG_HEAD_BIT) : r.cnt;
+      } else {
+        out_acc[j] = r.acc;
+        out_cnt[j] = r.cnt;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void seg_scan_apply_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
+    int64_t n, int op, int is_float, const int64_t* __restrict__ car_head,
+    const int64_t* __restrict__ car_acc, const int64_t* __restrict__ car_cnt,
+    int64_t* __restrict__ out_acc, int64_t* __restrict__ out_cnt) {
+  __shared__ SegVal ws[2][SEG_WAVES];
+  seg_scan_apply<false>(perm, pkeys, vals, valid, n, op, is_float, car_head,
+                        car_acc, car_cnt, out_acc, out_cnt, ws);
+}
+
+// ------------------------------------------------------------------ //
+// seg_total: whole-partition SUM/MIN/MAX/FIRST/LAST and COUNT           //
+//                                                                      //
+// Every row receives the aggregate of all non-null values of its       //
+// partition.  The forward pass is the running scan above, kept in      //
+// sorted-position order in scratch: its value at a partition's last    //
+// position IS the total, with the bits seg_scan gives there.  The      //
+// backward pass resolves, for every position, the last position of its //
+// partition (the nearest one at or after it whose successor starts a   //
+// partition), chunks chained by summary -> single-block scan -> apply  //
+// like everything here, and copies that position's (acc, cnt) to       //
+// out[perm[i]].  A copy, so all rows of a partition agree bit for bit; //
+// -1 marks "no partition end seen yet", which leaves cnt == 0 free to  //
+// be a payload.  The head bits in scratch spare the backward pass the  //
+// key gather.                                                          //
+// ------------------------------------------------------------------ //
+
+__global__ __launch_bounds__(BLOCK) void seg_total_forward_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
+    int64_t n, int op, int is_float, const int64_t* __restrict__ car_head,
+    const int64_t* __restrict__ car_acc, const int64_t* __restrict__ car_cnt,
+    int64_t* __restrict__ fwd_acc, int64_t* __restrict__ fwd_cnt) {
+  __shared__ SegVal ws[2][SEG_WAVES];
+  seg_scan_apply<true>(perm, pkeys, vals, valid, n, op, is_float, car_head,
+                       car_acc, car_cnt, fwd_acc, fwd_cnt, ws);
+}
+
+// is sorted position i (< n) the last of its partition?
+__device__ __forceinline__ bool seg_is_tail(const int64_t* __restrict__ fwd_cnt,
+                                            int64_t i, int64_t n) {
+  return i + 1 >= n || fwd_cnt[i + 1] < 0;
+}
+
+// first partition end of each chunk, -1 if it has none
+__global__ __launch_bounds__(BLOCK) void seg_total_summary_kernel(
+    const int64_t* __restrict__ fwd_cnt, int64_t n,
+    int64_t* __restrict__ sum_tail) {
+  __shared__ int s_tail;
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  if (threadIdx.x == 0) s_tail = SEG_CHUNK;
+  __syncthreads();
+  int ltail = SEG_CHUNK;
+  for (int it = SEG_ITERS - 1; it >= 0; --it) {
+    int rel = it * BLOCK + (int)threadIdx.x;
+    int64_t i = start + rel;
+    if (i < n && seg_is_tail(fwd_cnt, i, n)) ltail = rel;
+  }
+  if (ltail < SEG_CHUNK) atomicMin(&s_tail, ltail);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    sum_tail[blockIdx.x] = s_tail < SEG_CHUNK ? start + s_tail : -1;
+}
+
+// single-block exclusive scan from the right: chunk b receives the first
+// partition end of chunks (b, nblocks), -1 if there is none
+__global__ __launch_bounds__(BLOCK) void seg_total_scan_kernel(
+    const int64_t* __restrict__ sum_tail, int nblocks,
+    int64_t* __restrict__ car_tail) {
+  __shared__ int64_t tile[BLOCK];
+  int64_t carry = -1;  // same value in every thread
+  int ntiles = (nblocks + BLOCK - 1) / BLOCK;
+  for (int t = ntiles - 1; t >= 0; --t) {
+    int i = t * BLOCK + (int)threadIdx.x;
+    tile[threadIdx.x] = i < nblocks ? sum_tail[i] : -1;
+    __syncthreads();
+    for (int off = 1; off < BLOCK; off <<= 1) {
+      int64_t self = tile[threadIdx.x];
+      int64_t right = -1;
+      if ((int)threadIdx.x + off < BLOCK) right = tile[threadIdx.x + off];
+      __syncthreads();
+      if (self < 0) tile[threadIdx.x] = right;
+      __syncthreads();
+    }
+    if (i < nblocks) {
+      int64_t e = threadIdx.x + 1 < BLOCK ? tile[threadIdx.x + 1] : -1;
+      car_tail[i] = e >= 0 ? e : carry;
+    }
+    if (tile[0] >= 0) carry = tile[0];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void seg_total_apply_kernel(
+    const int64_t* __restrict__ perm, int64_t n,
+    const int64_t* __restrict__ car_tail, const int64_t* __restrict__ fwd_acc,
+    const int64_t* __restrict__ fwd_cnt, int64_t* __restrict__ out_acc,
+    int64_t* __restrict__ out_cnt) {
+  __shared__ int64_t ws[2][SEG_WAVES];
+  int64_t start = (int64_t)blockIdx.x * SEG_CHUNK;
+  int lane = threadIdx.x % WAVE;
+  int wave = threadIdx.x / WAVE;
+  int64_t carry = car_tail[blockIdx.x];  // same value in every thread
+  for (int it = SEG_ITERS - 1; it >= 0; --it) {
+    int64_t i0 = start + (int64_t)it * BLOCK;
+    if (i0 >= n) continue;  // block-uniform
+    int64_t i = i0 + threadIdx.x;
+    int64_t w0 = i0 + (int64_t)wave * WAVE;
+    uint64_t tmask = __ballot(i < n && seg_is_tail(fwd_cnt, i, n));
+    if (lane == 0)
+      ws[it & 1][wave] = tmask != 0 ? w0 + __ffsll((long long)tmask) - 1 : -1;
+    __syncthreads();
+    // nearest end in a later wave of these 256 positions, else the carry
+    int64_t in = carry;
+    int64_t tot = carry;
+#pragma unroll
+    for (int w = SEG_WAVES - 1; w >= 0; --w) {
+      int64_t s = ws[it & 1][w];
+      if (s >= 0) {
+        if (w > wave) in = s;
+        tot = s;
+      }
+    }
+    carry = tot;
+    uint64_t m = tmask & (~0ULL << lane);  // lanes >= this one
+    int64_t t = m != 0 ? w0 + __ffsll((long long)m) - 1 : in;
+    if (i < n) {
+      int64_t j = seg_row(perm, i, n);
+      // position n - 1 always ends a partition, so t is in [i, n); the
+      // test keeps a corrupted scratch from reading out of bounds
+      bool ok = (uint64_t)t < (uint64_t)n;
+      out_acc[j] = ok ? fwd_acc[t] : 0;
+      out_cnt[j] = ok ? (fwd_cnt[t] & ~SEG_HEAD_BIT) : 0;
     }
   }
 }
@@ -761,6 +917,38 @@ void launch_seg_scan(const int64_t* perm, const int64_t* pkeys,
                      stream, perm, pkeys, vals, valid, n, op, is_float,
                      w + 3 * (int64_t)nblocks, w + 4 * (int64_t)nblocks,
                      w + 5 * (int64_t)nblocks, out_acc, out_cnt);
+}
+
+// work: SEG_TOTAL_WORK(n) int64: the scan's 6 * nblocks, the backward
+// pass's 2 * nblocks, then the forward values (acc, cnt) of n positions
+void launch_seg_total(const int64_t* perm, const int64_t* pkeys,
+                      const int64_t* vals, const uint8_t* valid, int64_t n,
+                      int op, int is_float, int64_t* work, int64_t* out_acc,
+                      int64_t* out_cnt, hipStream_t stream) {
+  if (n <= 0) return;
+  int nblocks = (int)((n + SEG_CHUNK - 1) / SEG_CHUNK);
+  int64_t nb = nblocks;
+  int64_t* w = work;
+  int64_t* sum_tail = w + 6 * nb;
+  int64_t* car_tail = w + 7 * nb;
+  int64_t* fwd_acc = w + 8 * nb;
+  int64_t* fwd_cnt = fwd_acc + n;
+  hipLaunchKernelGGL(seg_scan_summary_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, vals, valid, n, op, is_float, w,
+                     w + nb, w + 2 * nb);
+  hipLaunchKernelGGL(seg_scan_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, w,
+                     w + nb, w + 2 * nb, nblocks, op, is_float, w + 3 * nb,
+                     w + 4 * nb, w + 5 * nb);
+  hipLaunchKernelGGL(seg_total_forward_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, vals, valid, n, op, is_float,
+                     w + 3 * nb, w + 4 * nb, w + 5 * nb, fwd_acc, fwd_cnt);
+  hipLaunchKernelGGL(seg_total_summary_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, fwd_cnt, n, sum_tail);
+  hipLaunchKernelGGL(seg_total_scan_kernel, dim3(1), dim3(BLOCK), 0, stream,
+                     sum_tail, nblocks, car_tail);
+  hipLaunchKernelGGL(seg_total_apply_kernel, dim3(nblocks), dim3(BLOCK), 0,
+                     stream, perm, n, car_tail, fwd_acc, fwd_cnt, out_acc,
+                     out_cnt);
 }
 
 }  // extern "C"

@@ -1892,6 +1892,186 @@ class HipExecutionEngine(ExecutionEngine):
             self._stats.add("window.device_value")
         return HipDataFrame.from_columns(cols, schema, self._device)
 
+    _PARTITION_WINDOW_FUNCS = (
+        "sum", "min", "max", "count", "avg", "first_value", "last_value"
+    )
+
+    def _check_partition_items(self, d: HipDataFrame, items: List[Any]) -> bool:
+        """Checks of ``partition_over`` that read the schema and the
+        arguments only.  Returns whether some item reads an integer
+        column (see ``_check_value_items``)."""
+        names = set()
+        any_int = False
+        for name, func, arg in items:
+            if func not in self._PARTITION_WINDOW_FUNCS:
+                raise NotImplementedError(f"window function {func}")
+            if name in d.schema or name in names:
+                raise NotImplementedError(f"column {name} already exists")
+            names.add(name)
+            if arg is None:
+                if func != "count":
+                    raise NotImplementedError(f"{func} needs an argument")
+                continue
+            if arg not in d.schema:
+                raise NotImplementedError(f"column {arg} not in the frame")
+            tp = d.schema[arg].type
+            is_int = pa.types.is_signed_integer(tp)
+            if not (is_int or pa.types.is_floating(tp)) or isinstance(
+                d.col(arg), StringDeviceColumn
+            ):
+                # strings, nested, bool, dates: the host's types differ
+                raise NotImplementedError(f"window over a {tp} column")
+            any_int |= is_int
+            if func in ("sum", "avg") and tp == pa.float32():
+                # pandas sums (and averages) a float32 group in float32
+                raise NotImplementedError(f"{func} of a float column")
+        return any_int
+
+    def partition_over(
+        self,
+        df: DataFrame,
+        partition_by: List[str],
+        order_by: List[Tuple[str, bool]],
+        items: List[Tuple[str, str, Optional[str]]],
+    ) -> DataFrame:
+        """``df`` plus one whole-partition window column per item, all
+        over (PARTITION BY ``partition_by`` ORDER BY ``order_by``): every
+        row receives the value of its whole partition.  Each item is
+        ``(name, func, arg_column)`` with ``func`` in ``sum`` / ``min`` /
+        ``max`` / ``count`` / ``avg`` / ``first_value`` / ``last_value``;
+        ``count`` with ``arg_column=None`` is ``COUNT(*)``, the partition
+        size.  ``first_value`` / ``last_value`` are the first / last
+        non-null value in sorted order (nulls last, ties in original row
+        order; original row order when ``order_by`` is empty); the order
+        does not change the other functions.  Values and types are the
+        host SQL executor's (table in ``sql/planner.py``).  Raises
+        ``NotImplementedError`` for shapes that stay on the host."""
+        d = self.to_df(df)
+        if not isinstance(d, HipDataFrame):
+            raise NotImplementedError("partition_over needs a device frame")
+        if os.environ.get("FUGUE_HIP_FORCE_HOST_WINDOW", "") == "1":
+            # A/B probe (benchmarks/window_bench.py): the host path
+            raise NotImplementedError("host window forced")
+        if len(partition_by) == 0:
+            raise NotImplementedError("window without PARTITION BY")
+        if len(items) == 0:
+            raise NotImplementedError("no window items")
+        order_names = [c for c, _ in order_by]
+        order_asc = [bool(a) for _, a in order_by]
+        keys = list(partition_by)
+        items = [tuple(it) for it in items]
+        any_int = self._check_partition_items(d, items)
+        self._check_rank_shape(d, keys, order_names)
+        if any_int:
+            # as in window_over: an integer column under a validity mask
+            # reaches the host as another type; the ranks decide together
+            masked = int(
+                any(
+                    it[2] is not None
+                    and pa.types.is_integer(d.schema[it[2]].type)
+                    and d.col(it[2]).valid is not None
+                    for it in items
+                )
+            )
+            if self.is_distributed:
+                masked = int(self._comm.allreduce_sum(masked))
+            if masked > 0:
+                raise NotImplementedError("nullable integer window column")
+        total = d.count()
+        if self.is_distributed:
+            total = int(self._comm.allreduce_sum(total))
+        if total == 0:
+            # the host executor types an empty window column as double
+            raise NotImplementedError("window over an empty frame")
+        new_cols: Dict[str, DeviceColumn] = {}
+        with op_range("fugue.window.partition"):
+            if self.is_distributed:
+                d = self._shuffle_by_columns(d, keys)
+            pkeys, perm = self._partition_sort(
+                d, keys, order_names, order_asc, "last"
+            )
+            totals: Dict[Tuple[str, str], Tuple[torch.Tensor, torch.Tensor]] = {}
+
+            def _total(arg: str, func: str, as_double: bool = False):
+                key = (arg, func + ("/f64" if as_double else ""))
+                if key not in totals:
+                    c = d.col(arg)
+                    col: Any = c
+                    if as_double:
+                        col = (c.data.to(torch.float64), c.valid)
+                    totals[key] = dops.segmented_total(perm, pkeys, col, func)
+                return totals[key]
+
+            def _any_count(arg: Optional[str]) -> torch.Tensor:
+                # the count comes with every total: take one that exists
+                for (a, _f), (_acc, cnt) in totals.items():
+                    if a == arg:
+                        return cnt
+                return _total(arg, "sum")[1]
+
+            star: Optional[torch.Tensor] = None
+            for name, func, arg in items:
+                if arg is None:  # COUNT(*): the partition size
+                    if star is None:
+                        ones = torch.ones_like(pkeys)
+                        star = dops.segmented_total(
+                            perm, pkeys, (ones, None), "sum"
+                        )[1]
+                    new_cols[name] = DeviceColumn(star, None, pa.int64())
+                    continue
+                c = d.col(arg)
+                tp = d.schema[arg].type
+                if func == "count":
+                    new_cols[name] = DeviceColumn(
+                        _any_count(arg), None, pa.int64()
+                    )
+                elif func == "avg":
+                    acc, cnt = _total(arg, "sum", as_double=True)
+                    some = cnt > 0
+                    mean = acc / torch.where(some, cnt, torch.ones_like(cnt))
+                    new_cols[name] = DeviceColumn(mean, some, pa.float64())
+                elif func == "sum":
+                    acc, _ = _total(arg, "sum")
+                    out_tp = tp
+                    if pa.types.is_integer(tp) and tp != pa.int64():
+                        # pandas sums in int64 and narrows the result back
+                        # only if every total fits the input type
+                        info = torch.iinfo(c.data.dtype)
+                        wide = int(
+                            bool(
+                                ((acc < info.min) | (acc > info.max))
+                                .any()
+                                .item()
+                            )
+                        )
+                        if self.is_distributed:
+                            wide = int(self._comm.allreduce_sum(wide))
+                        if wide > 0:
+                            out_tp = pa.int64()
+                    if out_tp == tp:
+                        acc = acc.to(c.data.dtype)
+                    # the sum of an all-null partition is 0, not null
+                    new_cols[name] = DeviceColumn(acc, None, out_tp)
+                else:
+                    op = {"first_value": "first", "last_value": "last"}.get(
+                        func, func
+                    )
+                    acc, cnt = _total(arg, op)
+                    out_valid: Optional[torch.Tensor] = None
+                    if c.data.is_floating_point():
+                        out_valid = cnt > 0  # only floats carry nulls here
+                    new_cols[name] = DeviceColumn(
+                        acc.to(c.data.dtype), out_valid, tp
+                    )
+        cols = dict(d.columns_map)
+        cols.update(new_cols)
+        schema = d.schema + Schema(
+            [(n, c.pa_type) for n, c in new_cols.items()]
+        )
+        for _ in items:
+            self._stats.add("window.device_partition")
+        return HipDataFrame.from_columns(cols, schema, self._device)
+
     # ------------------------------------------------------------------ #
     # select / aggregate: device fast path                                 #
     # ------------------------------------------------------------------ #

@@ -1895,8 +1895,10 @@ def _segmented_scan_cpu(
             both = la + ra  # int64 wraps like the unsigned device add
         elif op == 1:
             both = torch.where(ra < la, ra, la)
-        else:
+        elif op == 2:
             both = torch.where(ra > la, ra, la)
+        else:  # first / last non-null value (segmented_total only)
+            both = la if op == 3 else ra
         merged = torch.where(lc == 0, ra, torch.where(rc == 0, la, both))
         new_acc = torch.where(rf, ra, merged)
         new_cnt = torch.where(rf, rc, lc + rc)
@@ -1935,6 +1937,59 @@ def segmented_scan(
             cnt[perm] = c
         return acc, cnt
     acc, cnt = get_ext().seg_scan(perm, pkeys, data, valid, op)
+    return acc, cnt
+
+
+TOTAL_FUNCS = {"sum": 0, "min": 1, "max": 2, "first": 3, "last": 4}
+
+
+def _segmented_total_cpu(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    data: torch.Tensor,
+    valid: Optional[torch.Tensor],
+    op: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(acc, cnt) per SORTED position: the running scan's value at the
+    last position of the partition, copied to all of its positions."""
+    n = perm.numel()
+    acc, cnt = _segmented_scan_cpu(perm, pkeys, data, valid, op)
+    head, _ = _segment_flags_cpu(perm, pkeys, [])
+    tail = torch.ones(n, dtype=torch.bool)
+    tail[:-1] = head[1:]
+    seg = torch.cumsum(head.to(torch.int64), 0) - 1
+    last = torch.nonzero(tail).reshape(-1).index_select(0, seg)
+    return acc.index_select(0, last), cnt.index_select(0, last)
+
+
+def segmented_total(
+    perm: torch.Tensor, pkeys: torch.Tensor, col: Any, func: str
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Whole-partition ``sum`` / ``min`` / ``max`` / ``first`` / ``last``
+    of one value column, given to every row of the partition.  Returns
+    ``(acc, cnt)`` in ORIGINAL row order: ``cnt`` (int64) is the number of
+    non-null values of the row's partition and ``acc`` (int64 or float64)
+    their aggregate, 0 when ``cnt`` is 0.  ``first`` / ``last`` are the
+    first / last non-null value in sorted order.  All rows of a partition
+    hold the same bits, and for ``sum`` / ``min`` / ``max`` those are the
+    bits :func:`segmented_scan` yields at the partition's last sorted
+    position.  Integer sums wrap.  Inputs as :func:`segmented_scan`."""
+    if func not in TOTAL_FUNCS:
+        raise ValueError(f"unknown total function {func!r}")
+    op = TOTAL_FUNCS[func]
+    data, valid = _value_col_parts(col)
+    perm = perm.contiguous()
+    pkeys = pkeys.contiguous()
+    if _is_cpu(perm):
+        n = perm.numel()
+        acc = torch.empty_like(data)
+        cnt = torch.empty(n, dtype=torch.int64)
+        if n > 0:
+            a, c = _segmented_total_cpu(perm, pkeys, data, valid, op)
+            acc[perm] = a
+            cnt[perm] = c
+        return acc, cnt
+    acc, cnt = get_ext().seg_total(perm, pkeys, data, valid, op)
     return acc, cnt
 
 
