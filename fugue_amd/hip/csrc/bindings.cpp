@@ -874,6 +874,116 @@ std::vector<at::Tensor> join_emit_unique(
   return {out_pi, out_bi, cursor, out_mask};
 }
 
+namespace {
+// one operand of the join_unique_select comparison: (kind, value) with
+// kind JSEL_PROBE / JSEL_BUILD and a column of that side's length, or
+// JSEL_IMM and a Python int or float
+void jsel_operand(const py::handle& spec, int s, int64_t np, int64_t nb,
+                  JoinSelPred* p) {
+  auto t = py::cast<py::tuple>(spec);
+  TORCH_CHECK(t.size() == 2, "operand is (kind, value)");
+  int kind = py::cast<int>(t[0]);
+  p->kind[s] = kind;
+  if (kind == JSEL_IMM) {
+    if (py::isinstance<py::float_>(t[1])) {
+      double d = py::cast<double>(t[1]);
+      std::memcpy(&p->imm[s], &d, 8);
+      p->is_f64[s] = 1;
+    } else {
+      TORCH_CHECK(py::isinstance<py::int_>(t[1]) &&
+                      !py::isinstance<py::bool_>(t[1]),
+                  "immediate must be an int or a float");
+      p->imm[s] = (unsigned long long)py::cast<int64_t>(t[1]);
+      p->is_f64[s] = 0;
+    }
+    return;
+  }
+  TORCH_CHECK(kind == JSEL_PROBE || kind == JSEL_BUILD, "operand kind");
+  auto col = py::cast<at::Tensor>(t[1]);
+  check_gpu(col, "predicate column");
+  TORCH_CHECK(col.scalar_type() == at::kLong ||
+                  col.scalar_type() == at::kDouble,
+              "predicate columns are int64 or float64");
+  TORCH_CHECK(col.numel() == (kind == JSEL_PROBE ? np : nb),
+              "predicate column length does not match its side");
+  p->ptr[s] = reinterpret_cast<unsigned long long>(col.data_ptr());
+  p->is_f64[s] = col.scalar_type() == at::kDouble ? 1 : 0;
+}
+}  // namespace
+
+// Inner join against unique build keys with an optional residual
+// comparison and a projection, one kernel (join.hip).  heads/next: the
+// chained table of join_build over build_keys.  pred: None, or
+// (op, lhs, rhs) with op 0 == 1 != 2 < 3 <= 4 > 5 >= and operands as
+// jsel_operand takes them.  out_specs: up to COMPACT_MAX_COLS pairs
+// (side, column) of 8-byte columns, side 0 probe / 1 build.  Returns the
+// output columns at probe length (capacity mode) followed by the cursor
+// [1]: the caller narrows to its value.  Row order is not defined.  An
+// empty probe or build side returns empty columns without a launch.
+std::vector<at::Tensor> join_unique_select(
+    at::Tensor pkeys, at::Tensor bkeys, at::Tensor heads, at::Tensor next,
+    py::object pred, std::vector<std::pair<int64_t, at::Tensor>> out_specs) {
+  check_gpu(pkeys, "probe_keys");
+  check_gpu(bkeys, "build_keys");
+  check_gpu(heads, "heads");
+  check_gpu(next, "next");
+  TORCH_CHECK(pkeys.scalar_type() == at::kLong &&
+                  bkeys.scalar_type() == at::kLong,
+              "join keys must be int64");
+  TORCH_CHECK(heads.scalar_type() == at::kInt &&
+                  next.scalar_type() == at::kInt,
+              "heads/next must be int32");
+  TORCH_CHECK(out_specs.size() >= 1 && out_specs.size() <= COMPACT_MAX_COLS,
+              "1..", COMPACT_MAX_COLS, " output columns");
+  int64_t np = pkeys.numel(), nb = bkeys.numel();
+  int64_t tsize = heads.numel();
+  TORCH_CHECK(tsize > 0 && (tsize & (tsize - 1)) == 0,
+              "heads length must be a power of 2");
+  TORCH_CHECK(next.numel() >= nb, "next is shorter than the build side");
+  TORCH_CHECK(nb <= std::numeric_limits<int32_t>::max(),
+              "build side too long for int32 chain links");
+  bool empty = np == 0 || nb == 0;
+  JoinSelPred p;
+  std::memset(&p, 0, sizeof(p));
+  p.op = -1;
+  if (!pred.is_none()) {
+    auto t = py::cast<py::tuple>(pred);
+    TORCH_CHECK(t.size() == 3, "pred is (op, lhs, rhs)");
+    p.op = py::cast<int>(t[0]);
+    TORCH_CHECK(p.op >= 0 && p.op <= 5, "comparison op code 0..5");
+    jsel_operand(t[1], 0, np, nb, &p);
+    jsel_operand(t[2], 1, np, nb, &p);
+    p.use_int = (!p.is_f64[0] && !p.is_f64[1]) ? 1 : 0;
+  }
+  JoinSelCols c;
+  std::memset(&c, 0, sizeof(c));
+  c.ncols = (int)out_specs.size();
+  std::vector<at::Tensor> outs;
+  for (size_t i = 0; i < out_specs.size(); ++i) {
+    int64_t side = out_specs[i].first;
+    const at::Tensor& col = out_specs[i].second;
+    TORCH_CHECK(side == JSEL_PROBE || side == JSEL_BUILD, "column side");
+    check_gpu(col, "output column");
+    TORCH_CHECK(col.element_size() == 8, "8-byte columns only");
+    TORCH_CHECK(col.numel() == (side == JSEL_PROBE ? np : nb),
+                "output column length does not match its side");
+    auto out = at::empty({empty ? 0 : np}, col.options());
+    c.side[i] = (int)side;
+    c.src[i] = reinterpret_cast<unsigned long long>(col.data_ptr());
+    c.dst[i] = reinterpret_cast<unsigned long long>(out.data_ptr());
+    outs.push_back(out);
+  }
+  auto cursor = at::zeros({1}, pkeys.options());
+  if (!empty) {
+    launch_join_unique_select(
+        pkeys.data_ptr<int64_t>(), np, bkeys.data_ptr<int64_t>(),
+        heads.data_ptr<int32_t>(), next.data_ptr<int32_t>(), tsize, &p, &c,
+        cursor.data_ptr<int64_t>(), current_stream());
+  }
+  outs.push_back(cursor);
+  return outs;
+}
+
 at::Tensor join_count(at::Tensor pkeys, at::Tensor bkeys,
                       c10::optional<at::Tensor> ph2,
                       c10::optional<at::Tensor> bh2, at::Tensor heads,
@@ -1682,7 +1792,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bin_group_base"), py::arg("bin_chunk_base"),
         py::arg("total_chunks"), py::arg("n_groups"), py::arg("chunk"),
         py::arg("slots"), py::arg("tile"), py::arg("threads") = 0);
+  m.attr("COMPACT_CHUNK") = (int64_t)COMPACT_CHUNK;
+  m.attr("COMPACT_MAX_COLS") = (int64_t)COMPACT_MAX_COLS;
   m.def("join_build",&join_build, "build chained hash table");
+  m.def("join_unique_select", &join_unique_select,
+        "unique inner join + residual comparison + projection, one pass",
+        py::arg("probe_keys"), py::arg("build_keys"), py::arg("heads"),
+        py::arg("next"), py::arg("pred"), py::arg("out_specs"));
   m.def("join_emit_unique", &join_emit_unique,
         "single-pass join emit for unique build keys");
   m.def("hash_string_column", &hash_string_column,

@@ -95,3 +95,17 @@ __device__ __forceinline__ void atomic_max_f64(double* addr, double val) {
     old = atomicCAS(a, assumed, __double_as_longlong(val));
   } while (old != assumed);
 }
+
+// one comparison in domain CT; op codes 0 == 1 != 2 < 3 <= 4 > 5 >= (the
+// single-comparison filters of select.hip and join_unique_select)
+template <typename CT>
+__device__ __forceinline__ bool cmp_apply(CT a, CT b, int op) {
+  switch (op) {
+    case 0: return a == b;
+    case 1: return a != b;
+    case 2: return a < b;
+    case 3: return a <= b;
+    case 4: return a > b;
+    default: return a >= b;
+  }
+}

@@ -361,7 +361,136 @@ __global__ __launch_bounds__(BLOCK) void join_mark_build_kernel(
   }
 }
 
+// ------------------------------------------------------------------ //
+// fused unique inner join + residual comparison + projection          //
+//                                                                     //
+// One block per COMPACT_CHUNK probe rows, grid-stride.  Phase A is the //
+// ILP-4 chain walk of join_left_unique_kernel over the block's chunk   //
+// (the dependent random loads heads -> bkeys/next bound the kernel);   //
+// the comparison runs on the matched rows and the surviving match      //
+// index stays in LDS.  Phase B reserves one output range per block     //
+// (LDS counter, ONE global atomic, as compact8_kernel).  Phase C       //
+// writes the projected columns, probe-side at the probe row and        //
+// build-side at the match, straight into the range: no bi/mask arrays, //
+// no materialised join result, no second compaction.                   //
+// ------------------------------------------------------------------ //
+
+__device__ __forceinline__ long long jsel_operand(const JoinSelPred& p, int s,
+                                                  int64_t i, int32_t m) {
+  if (p.kind[s] == JSEL_IMM) return (long long)p.imm[s];
+  const long long* col = reinterpret_cast<const long long*>(p.ptr[s]);
+  return p.kind[s] == JSEL_BUILD ? col[m] : col[i];
+}
+
+// int64/int64 compares exactly; anything else in fp64 as cmp_col_kernel
+// does (so a NaN operand fails every OP but !=, IEEE as there)
+__device__ __forceinline__ bool jsel_pred(const JoinSelPred& p, int64_t i,
+                                          int32_t m) {
+  if (p.op < 0) return true;
+  long long a = jsel_operand(p, 0, i, m);
+  long long b = jsel_operand(p, 1, i, m);
+  if (p.use_int) return cmp_apply<long long>(a, b, p.op);
+  double x = p.is_f64[0] ? __longlong_as_double(a) : (double)a;
+  double y = p.is_f64[1] ? __longlong_as_double(b) : (double)b;
+  return cmp_apply<double>(x, y, p.op);
+}
+
+__global__ __launch_bounds__(BLOCK) void join_unique_select_kernel(
+    const int64_t* __restrict__ pkeys, int64_t np,
+    const int64_t* __restrict__ bkeys, const int32_t* __restrict__ heads,
+    const int32_t* __restrict__ next, int64_t tsize, JoinSelPred pred,
+    JoinSelCols cols, int64_t* __restrict__ cursor) {
+  __shared__ int32_t smatch[COMPACT_CHUNK];  // surviving match or -1
+  __shared__ int lcount;
+  __shared__ long long lbase;
+  uint64_t tmask = (uint64_t)(tsize - 1);
+  for (int64_t start = (int64_t)blockIdx.x * COMPACT_CHUNK; start < np;
+       start += (int64_t)gridDim.x * COMPACT_CHUNK) {
+    int64_t end = start + COMPACT_CHUNK;
+    if (end > np) end = np;
+    if (threadIdx.x == 0) lcount = 0;
+    __syncthreads();
+    int local = 0;
+    for (int g = 0; g < COMPACT_CHUNK / BLOCK; g += 4) {
+      int64_t idx[4], key[4];
+      int32_t cur[4], match[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        idx[j] = start + (int64_t)(g + j) * BLOCK + threadIdx.x;
+        match[j] = -1;
+        if (idx[j] < end) {
+          key[j] = pkeys[idx[j]];
+          cur[j] = heads[(int64_t)(mix64((uint64_t)key[j]) & tmask)];
+        } else {
+          cur[j] = -1;
+        }
+      }
+      bool any = true;
+      while (any) {
+        any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (cur[j] >= 0) {
+            int32_t c = cur[j];
+            if (bkeys[c] == key[j]) {
+              match[j] = c;
+              cur[j] = -1;
+            } else {
+              cur[j] = next[c];
+              if (cur[j] >= 0) any = true;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (match[j] >= 0 && !jsel_pred(pred, idx[j], match[j])) match[j] = -1;
+        smatch[(g + j) * BLOCK + threadIdx.x] = match[j];
+        if (match[j] >= 0) ++local;
+      }
+    }
+    atomicAdd(&lcount, local);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      lbase = lcount > 0
+                  ? (long long)atomicAdd((unsigned long long*)cursor,
+                                         (unsigned long long)lcount)
+                  : 0;
+      lcount = 0;
+    }
+    __syncthreads();
+    // a thread reads back only the slots it wrote
+    for (int r = 0; r < COMPACT_CHUNK / BLOCK; ++r) {
+      int32_t m = smatch[r * BLOCK + threadIdx.x];
+      if (m < 0) continue;
+      int64_t i = start + (int64_t)r * BLOCK + threadIdx.x;
+      int64_t pos = (int64_t)lbase + atomicAdd(&lcount, 1);
+#pragma unroll
+      for (int c = 0; c < COMPACT_MAX_COLS; ++c) {
+        if (c < cols.ncols) {
+          const uint64_t* src = reinterpret_cast<const uint64_t*>(cols.src[c]);
+          reinterpret_cast<uint64_t*>(cols.dst[c])[pos] =
+              cols.side[c] == JSEL_BUILD ? src[m] : src[i];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 extern "C" {
+
+void launch_join_unique_select(const int64_t* pkeys, int64_t np,
+                               const int64_t* bkeys, const int32_t* heads,
+                               const int32_t* next, int64_t tsize,
+                               const JoinSelPred* pred,
+                               const JoinSelCols* cols, int64_t* cursor,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(join_unique_select_kernel,
+                     dim3(chunk_grid(np, COMPACT_CHUNK)), dim3(BLOCK), 0,
+                     stream, pkeys, np, bkeys, heads, next, tsize, *pred,
+                     *cols, cursor);
+}
 
 void launch_join_build(const int64_t* keys, int64_t n, int32_t* heads,
                        int32_t* next, int64_t tsize, int32_t* dup,

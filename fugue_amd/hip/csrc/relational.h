@@ -40,6 +40,30 @@
 // fused gather: most columns of one element width per launch
 #define GATHER_MAX_COLS 16
 
+// chunked compaction (compact8, join_unique_select): rows per block and
+// reservation, most 8-byte columns per launch
+#define COMPACT_CHUNK (BLOCK * 16)
+#define COMPACT_MAX_COLS 8
+
+// join_unique_select: residual comparison `lhs OP rhs` and projection,
+// passed to the kernel by value.  An operand or output column is read on
+// the probe side at the probe row, on the build side at the matched row.
+enum { JSEL_PROBE = 0, JSEL_BUILD = 1, JSEL_IMM = 2 };
+struct JoinSelPred {
+  int op;       // -1: no predicate; else 0 == 1 != 2 < 3 <= 4 > 5 >=
+  int use_int;  // both operands int64: exact compare; else in fp64
+  int kind[2];  // JSEL_PROBE / JSEL_BUILD / JSEL_IMM
+  int is_f64[2];               // operand holds fp64 bits (else int64)
+  unsigned long long ptr[2];   // column base (kinds PROBE, BUILD)
+  unsigned long long imm[2];   // immediate bits (kind IMM)
+};
+struct JoinSelCols {
+  int ncols;
+  int side[COMPACT_MAX_COLS];  // JSEL_PROBE / JSEL_BUILD
+  unsigned long long src[COMPACT_MAX_COLS];
+  unsigned long long dst[COMPACT_MAX_COLS];
+};
+
 // expression interpreter program limits
 #define EXPR_MAX_OPS 48
 #define EXPR_MAX_COLS 12
@@ -233,6 +257,20 @@ void launch_join_mark_build(const int64_t* pkeys, int64_t np,
                             const int64_t* bh2, const int32_t* heads,
                             const int32_t* next, int64_t tsize, bool* bmatched,
                             hipStream_t stream);
+// inner join against UNIQUE build keys + residual comparison + projection
+// in one pass.  Contract: heads/next come from launch_join_build over
+// bkeys (tsize a power of two, every chain ends at -1); np >= 1; every
+// dst holds np elements (capacity mode); *cursor is 0 on entry and holds
+// the number of rows written on exit; rows land in no defined order.  Any
+// int64 key value is admitted.  A build key that occurs twice makes the
+// walk stop at the first match in chain order: the caller must not use
+// the result then.
+void launch_join_unique_select(const int64_t* pkeys, int64_t np,
+                               const int64_t* bkeys, const int32_t* heads,
+                               const int32_t* next, int64_t tsize,
+                               const JoinSelPred* pred,
+                               const JoinSelCols* cols, int64_t* cursor,
+                               hipStream_t stream);
 void launch_joinoa_build(const int64_t* bkeys, int64_t nb, int64_t* table,
                          int64_t tsize, int64_t* flags, hipStream_t stream);
 void launch_joinoa_probe(const int64_t* pkeys, int64_t np,

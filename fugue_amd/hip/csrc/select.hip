@@ -292,8 +292,6 @@ void launch_expr_value(const ExprProg* prog, int64_t n, int out_int,
 // for its chunk (one global atomic), so writes coalesce; output order is
 // block-nondeterministic (frames are unordered collections).
 // ------------------------------------------------------------------ //
-#define COMPACT_CHUNK (BLOCK * 16)
-
 __global__ __launch_bounds__(BLOCK) void compact8_kernel(
     const bool* __restrict__ mask, int64_t n,
     int64_t* __restrict__ cursor,  // [1]
@@ -367,18 +365,6 @@ void launch_compact8(const bool* mask, int64_t n, int64_t* cursor,
 // simple `col < imm` predicate (profiles r02c).  Single comparisons   //
 // — the dominant WHERE shape — get dedicated one-pass kernels.        //
 // ------------------------------------------------------------------ //
-
-template <typename CT>
-__device__ __forceinline__ bool cmp_apply(CT a, CT b, int op) {
-  switch (op) {
-    case 0: return a == b;
-    case 1: return a != b;
-    case 2: return a < b;
-    case 3: return a <= b;
-    case 4: return a > b;
-    default: return a >= b;
-  }
-}
 
 // col vs immediate; CT is the comparison domain (int64_t or double)
 template <typename T, typename CT>

@@ -806,12 +806,44 @@ class HipExecutionEngine(ExecutionEngine):
         with op_range(f"fugue.join.{how}"):
             return self._join_impl(df1, df2, how, on)
 
+    def join_select(
+        self,
+        df1: DataFrame,
+        df2: DataFrame,
+        how: str,
+        on: Optional[List[str]],
+        cols: SelectColumns,
+        where: Optional[ColumnExpr] = None,
+    ) -> DataFrame:
+        """``select(join(df1, df2, how, on), cols, where=where)`` for an
+        inner join whose consumer is a projection of plain columns and at
+        most one comparison of columns and literals.  Where the frames
+        allow it (``_fused_join_select``) the join, the comparison and
+        the projection run as one kernel and the joined frame is never
+        materialised; otherwise the join and the select run one after the
+        other as before.  Raises NotImplementedError, before any work,
+        for every other request shape and with ``FUGUE_JOIN_FUSED=0``."""
+        post = _post_join_request(cols, where)
+        if (
+            post is None
+            or os.environ.get("FUGUE_JOIN_FUSED", "1") == "0"
+            or parse_join_type(how) != "inner"
+        ):
+            raise NotImplementedError("join_select: request shape")
+        self._stats.add("joins")
+        with op_range("fugue.join.inner"):
+            res = self._join_impl(df1, df2, how, on, post=post)
+        if not post.done:
+            res = self.select(res, cols, where=where)
+        return res
+
     def _join_impl(
         self,
         df1: DataFrame,
         df2: DataFrame,
         how: str,
         on: Optional[List[str]] = None,
+        post: "Optional[_PostJoin]" = None,
     ) -> DataFrame:
         how = parse_join_type(how)
         d1 = self.to_df(df1)
@@ -824,7 +856,7 @@ class HipExecutionEngine(ExecutionEngine):
         ):
             try:
                 return self._device_join(
-                    d1, d2, how, key_schema.names, output_schema
+                    d1, d2, how, key_schema.names, output_schema, post=post
                 )
             except NotImplementedError:
                 pass
@@ -929,7 +961,11 @@ class HipExecutionEngine(ExecutionEngine):
         how: str,
         keys: List[str],
         output_schema: Schema,
+        post: "Optional[_PostJoin]" = None,
     ) -> DataFrame:
+        """``post``: the join's consumer (``join_select``).  Answered here,
+        with ``post.done`` set, only by the fused local join; the
+        broadcast and co-shuffle steps before it are the same either way."""
         # null keys never match: split them out first
         d1v, d1n = self._split_null_keys(d1, keys)
         d2v, _d2n = self._split_null_keys(d2, keys)
@@ -958,12 +994,21 @@ class HipExecutionEngine(ExecutionEngine):
                 "semi": "semi",
                 "anti": "anti",
             }[how]
+            if post is not None and how == "inner" and h21 is None:
+                fused = self._fused_join_select(d1v, d2v, k1, k2, post)
+                if fused is not None:
+                    post.done = True
+                    return fused
             if how == "inner" and k1.numel() * 4 < k2.numel():
                 # build the smaller side (left), probe with the right
-                bi2, pi2 = dops.hash_join_indices(k2, k1, "inner", h22, h21)
+                bi2, pi2 = dops.hash_join_indices(
+                    k2, k1, "inner", h22, h21, stats=self._stats
+                )
                 pi, bi = pi2, bi2
             else:
-                pi, bi = dops.hash_join_indices(k1, k2, mode, h21, h22)
+                pi, bi = dops.hash_join_indices(
+                    k1, k2, mode, h21, h22, stats=self._stats
+                )
             res = self._emit_join_output(
                 d1v, d2v, pi, bi, keys, output_schema, probe_is_left=True,
                 may_have_unmatched=(mode == "left"),
@@ -973,7 +1018,9 @@ class HipExecutionEngine(ExecutionEngine):
                 res = res.concat_with([nulls])
             return res
         if how == "right_outer":
-            pi, bi = dops.hash_join_indices(k2, k1, "left", h22, h21)
+            pi, bi = dops.hash_join_indices(
+                k2, k1, "left", h22, h21, stats=self._stats
+            )
             res = self._emit_join_output(
                 d2v, d1v, pi, bi, keys, output_schema, probe_is_left=False
             )
@@ -982,7 +1029,9 @@ class HipExecutionEngine(ExecutionEngine):
                 res = res.concat_with([nulls])
             return res
         if how == "full_outer":
-            pi, bi = dops.hash_join_indices(k1, k2, "left", h21, h22)
+            pi, bi = dops.hash_join_indices(
+                k1, k2, "left", h21, h22, stats=self._stats
+            )
             res = self._emit_join_output(
                 d1v, d2v, pi, bi, keys, output_schema, probe_is_left=True
             )
@@ -1001,6 +1050,77 @@ class HipExecutionEngine(ExecutionEngine):
                 res = res.concat_with(parts)
             return res
         raise NotImplementedError(how)
+
+    def _fused_join_select(
+        self,
+        d1: HipDataFrame,
+        d2: HipDataFrame,
+        k1: torch.Tensor,
+        k2: torch.Tensor,
+        post: "_PostJoin",
+    ) -> Optional[HipDataFrame]:
+        """The local inner join on exact int64 keys with its consumer, as
+        one ``join_unique_select`` kernel; None when the frames do not fit
+        (CPU tensors, a null mask, a string or narrow column, duplicated
+        build keys) and the caller runs join and select apart."""
+        if k1.device.type != "cuda" or k2.device.type != "cuda":
+            return None
+        # same build-side choice as the unfused join
+        left_is_probe = not (k1.numel() * 4 < k2.numel())
+
+        def _side(name: str) -> Optional[Tuple[int, torch.Tensor, Any]]:
+            # a name both sides carry is a key: it comes from the left
+            if name in d1.schema._index:
+                c, side = d1.col(name), (0 if left_is_probe else 1)
+            elif name in d2.schema._index:
+                c, side = d2.col(name), (1 if left_is_probe else 0)
+            else:
+                return None
+            if (
+                isinstance(c, StringDeviceColumn)
+                or c.valid is not None
+                or c.data.dtype not in (torch.int64, torch.float64)
+                or not c.data.is_contiguous()
+            ):
+                return None
+            return side, c.data, c.pa_type
+
+        specs: List[Tuple[int, torch.Tensor]] = []
+        fields = []
+        for src_name, out_name in post.columns:
+            s = _side(src_name)
+            if s is None:
+                return None
+            specs.append((s[0], s[1]))
+            fields.append(pa.field(out_name, s[2]))
+        pred = None
+        if post.where is not None:
+            code, operands = post.where
+            ops_: List[Tuple[int, Any]] = []
+            for kind, value in operands:
+                if kind == "col":
+                    s = _side(value)
+                    if s is None:
+                        return None
+                    ops_.append((s[0], s[1]))
+                else:
+                    ops_.append((2, value))
+            pred = (code, ops_[0], ops_[1])
+        if left_is_probe:
+            outs = dops.join_unique_select(k1, k2, pred, specs, self._stats)
+        else:
+            outs = dops.join_unique_select(k2, k1, pred, specs, self._stats)
+        if outs is None:
+            return None  # duplicated build keys
+        self._stats.add("join.fused_select")
+        return HipDataFrame.from_columns(
+            {
+                f.name: DeviceColumn(t, None, f.type)
+                for f, t in zip(fields, outs)
+            },
+            Schema(fields),
+            self._device,
+        )
 
     def _global_bytes(self, df: HipDataFrame) -> int:
         # one allreduce per distinct frame: repeated plans (plan cache,
@@ -2982,6 +3102,69 @@ class HipExecutionEngine(ExecutionEngine):
                     format_hint=format_hint, mode=mode, **kwargs
                 )
         self._comm.barrier()
+
+
+class _PostJoin:
+    """What the consumer of a join asks of it (``join_select``):
+    ``columns`` as (source name, output name) and ``where`` as None or
+    (comparison code of expr._CMP_OP_CODE, two operands ("col", name) /
+    ("lit", int or float)).  ``done`` is set by the join that answered it."""
+
+    def __init__(self, columns: List[Tuple[str, str]], where: Any):
+        self.columns = columns
+        self.where = where
+        self.done = False
+
+
+def _post_join_request(
+    cols: SelectColumns, where: Optional[ColumnExpr]
+) -> Optional[_PostJoin]:
+    """The request a fused join can answer, or None: 1 to 8 plain column
+    references with distinct output names, and no WHERE or one comparison
+    whose operands are plain columns and numeric literals."""
+    from fugue_amd.hip.expr import _CMP_OP_CODE
+
+    if cols.has_agg or cols.is_distinct:
+        return None
+    columns: List[Tuple[str, str]] = []
+    for c in cols.all_cols:
+        if (
+            not isinstance(c, _NamedColumnExpr)
+            or c.wildcard
+            or c.as_type is not None
+        ):
+            return None
+        columns.append((c.name, c.output_name))
+    if not 1 <= len(columns) <= 8:
+        return None
+    if len({o for _, o in columns}) != len(columns):
+        return None
+    request = None
+    if where is not None:
+        if not isinstance(where, _BinaryOpExpr) or where.as_type is not None:
+            return None
+        code = _CMP_OP_CODE.get(where.op)
+        if code is None:
+            return None
+        operands: List[Tuple[str, Any]] = []
+        for e in (where.left, where.right):
+            if isinstance(e, _NamedColumnExpr):
+                if e.wildcard or e.as_type is not None:
+                    return None
+                operands.append(("col", e.name))
+            elif isinstance(e, _LiteralColumnExpr) and e.as_type is None:
+                v = e.value
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    return None
+                if isinstance(v, int) and not -(1 << 63) <= v < (1 << 63):
+                    return None
+                operands.append(("lit", v))
+            else:
+                return None
+        if operands[0][0] == "lit" and operands[1][0] == "lit":
+            return None
+        request = (code, operands)
+    return _PostJoin(columns, request)
 
 
 def _referenced_cols(cols: SelectColumns) -> Optional[set]:

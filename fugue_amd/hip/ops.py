@@ -224,6 +224,21 @@ def rand_buckets(n: int, num_buckets: int, seed: Optional[int], device) -> torch
 _KEY_STATS_MEMO: "Dict[Tuple[int, ...], Tuple[Any, Any]]" = {}
 _KEY_STATS_MEMO_CAP = 128
 
+# join build-table reuse: the chained table (heads, next) of a build-key
+# tensor and its duplicate flag depend on nothing but the keys, and a
+# persistent dimension table is the same tensor on every call (iterating
+# driver, plan cache).  Keyed like _KEY_STATS_MEMO — (address, length,
+# dtype) plus a weakref to the key tensor that must still be alive — so a
+# repeated build side skips join_build, join_dup_check, the heads fill
+# and the flag readback.  heads is 4 B x tsize (2 to 4 slots per build
+# row) and next 4 B per row: 12 to 20 B per build row.  At most
+# _JOIN_BUILD_MEMO_CAP entries, first-in first-out; a table above
+# _JOIN_BUILD_MEMO_MAX_BYTES (256 MB, about 13M to 22M build rows) is
+# built per call and never kept.  FUGUE_JOIN_BUILD_MEMO=0 disables it.
+_JOIN_BUILD_MEMO: "Dict[Tuple[Any, ...], Tuple[Any, Any]]" = {}
+_JOIN_BUILD_MEMO_CAP = 4
+_JOIN_BUILD_MEMO_MAX_BYTES = 256 << 20
+
 # shuffle-layout reuse (Spark shuffle-reuse analog): for a repeated key
 # tensor, the partition layout is recorded once and fresh values replay
 # through it.  A plain entry caches the spill keys + per-row positions
@@ -1420,12 +1435,98 @@ def distinct_reps(h1: torch.Tensor, h2: torch.Tensor) -> torch.Tensor:
     return cc.narrow(0, 0, int(bases[-1].item()))
 
 
+@dataclass
+class _JoinBuild:
+    """Chained table of one build-key tensor.  ``dup`` is the duplicate
+    flag as a host int once some caller has read ``dup_dev`` back (it
+    rides in that caller's own readback), None until then."""
+
+    heads: torch.Tensor
+    nxt: torch.Tensor
+    tsize: int
+    dup_dev: torch.Tensor
+    dup: Optional[int] = None
+
+
+def _join_build_table(build_keys: torch.Tensor, stats: Any = None) -> _JoinBuild:
+    """The chained join table of ``build_keys``, from _JOIN_BUILD_MEMO when
+    this very tensor (same bytes, still alive) was built before."""
+    use_memo = os.environ.get("FUGUE_JOIN_BUILD_MEMO", "1") != "0"
+    key = (
+        build_keys.data_ptr(),
+        build_keys.numel(),
+        str(build_keys.dtype),
+        str(build_keys.device),
+    )
+    if use_memo:
+        hit = _JOIN_BUILD_MEMO.get(key)
+        if hit is not None:
+            ref, tab = hit
+            if ref() is not None:
+                if stats is not None:
+                    stats.add("join.build_memo_hit")
+                return tab
+            del _JOIN_BUILD_MEMO[key]
+        # tables of dead key tensors (join inputs computed per call) go
+        # before the new one is allocated: they never push a persistent
+        # table out, and their memory is free for this build
+        for k in [k for k, (r, _) in _JOIN_BUILD_MEMO.items() if r() is None]:
+            del _JOIN_BUILD_MEMO[k]
+    nb = int(build_keys.numel())
+    tsize = _next_pow2(max(16, nb * 2))
+    heads, nxt, dup = get_ext().join_build(build_keys, tsize)
+    tab = _JoinBuild(heads, nxt, tsize, dup)
+    if use_memo:
+        if stats is not None:
+            stats.add("join.build_memo_miss")
+        nbytes = 4 * (int(heads.numel()) + int(nxt.numel()))
+        if nbytes <= _JOIN_BUILD_MEMO_MAX_BYTES:
+            if len(_JOIN_BUILD_MEMO) >= _JOIN_BUILD_MEMO_CAP:
+                _JOIN_BUILD_MEMO.pop(next(iter(_JOIN_BUILD_MEMO)))
+            _JOIN_BUILD_MEMO[key] = (weakref.ref(build_keys), tab)
+    return tab
+
+
+def join_unique_select(
+    probe_keys: torch.Tensor,
+    build_keys: torch.Tensor,
+    pred: Optional[Tuple[int, Tuple[int, Any], Tuple[int, Any]]],
+    out_specs: List[Tuple[int, torch.Tensor]],
+    stats: Any = None,
+) -> Optional[List[torch.Tensor]]:
+    """Inner join on exact int64 keys against UNIQUE build keys, with a
+    residual comparison and a projection, in one kernel
+    (``ext.join_unique_select``): the projected columns, narrowed to the
+    surviving rows, in no defined order.  None when the build keys hold a
+    duplicate — the caller takes the count+emit join.
+
+    The walk is speculative on first sight of a build tensor: the
+    duplicate flag comes back in the same single readback as the row
+    total.  A table from _JOIN_BUILD_MEMO knows its flag already."""
+    tab = _join_build_table(build_keys, stats)
+    if tab.dup:
+        return None
+    outs = get_ext().join_unique_select(
+        probe_keys, build_keys, tab.heads, tab.nxt, pred, out_specs
+    )
+    if tab.dup is None:
+        flags = torch.cat([tab.dup_dev.reshape(1), outs[-1].reshape(1)]).cpu()
+        tab.dup = int(flags[0].item())
+        total = int(flags[1].item())
+        if tab.dup:
+            return None
+    else:
+        total = int(outs[-1].item())  # the step's only readback
+    return [t.narrow(0, 0, total) for t in outs[:-1]]
+
+
 def hash_join_indices(
     probe_keys: torch.Tensor,
     build_keys: torch.Tensor,
     how: str,
     probe_h2: Optional[torch.Tensor] = None,
     build_h2: Optional[torch.Tensor] = None,
+    stats: Any = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Join on exact int64 keys; returns (probe_idx, build_idx) where
     build_idx == -1 marks no-match rows (left/anti).
@@ -1479,9 +1580,13 @@ def hash_join_indices(
             # the same way — go straight to the duplicate-emit path
             skip_unique_walk = int(vals[0]) != 0 and int(vals[1]) == 0
 
-    tsize = _next_pow2(max(16, nb * 2))
-    heads, nxt, dup = ext.join_build(build_keys, tsize)
+    # a repeated build tensor takes its table and its duplicate flag from
+    # _JOIN_BUILD_MEMO: no build kernels, and no flag in the readback
+    tab = _join_build_table(build_keys, stats)
+    tsize, heads, nxt = tab.tsize, tab.heads, tab.nxt
     mode = {"inner": 0, "left": 1, "semi": 2, "anti": 3}[how]
+    if tab.dup:
+        skip_unique_walk = True  # known duplicates: count+emit directly
 
     if not skip_unique_walk and _os_j.environ.get(
         "FUGUE_JOIN_UNIQUE", "1"
@@ -1500,18 +1605,24 @@ def hash_join_indices(
             how == "left", how != "left", how == "anti",
         )
         if how == "left":
-            if int(dup.item()) == 0:
+            if tab.dup is None:
+                tab.dup = int(tab.dup_dev.item())
+            if tab.dup == 0:
                 return out_p, out_b
         else:
             # matched mask came out of the walk kernel itself;
             # None column = "emit the row index" (no arange materialized)
             cols = [None] if how == "anti" else [None, out_b]
             outs = ext.compact_columns_cap(matched, cols)
-            flags = torch.cat(
-                [dup.reshape(1), outs[-1].reshape(1)]
-            ).cpu()
-            if int(flags[0].item()) == 0:
+            if tab.dup is None:
+                flags = torch.cat(
+                    [tab.dup_dev.reshape(1), outs[-1].reshape(1)]
+                ).cpu()
+                tab.dup = int(flags[0].item())
                 total = int(flags[1].item())
+            else:
+                total = int(outs[-1].item())
+            if tab.dup == 0:
                 if how == "anti":
                     pi = outs[0].narrow(0, 0, total)
                     return pi, torch.full_like(pi, -1)
@@ -1570,10 +1681,10 @@ def mark_matched_build_rows(
         return torch.from_numpy(m["__m"].notna().to_numpy())
     ext = get_ext()
     nb = int(build_keys.numel())
-    tsize = _next_pow2(max(16, nb * 2))
-    heads, nxt, _dup = ext.join_build(build_keys, tsize)
+    tab = _join_build_table(build_keys)
     return ext.join_mark_build(
-        probe_keys, build_keys, probe_h2, build_h2, heads, nxt, tsize, nb
+        probe_keys, build_keys, probe_h2, build_h2, tab.heads, tab.nxt,
+        tab.tsize, nb
     )
 
 

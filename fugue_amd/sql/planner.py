@@ -583,6 +583,75 @@ def _find_value_windows(
     return over[0], over[1], items
 
 
+_COMPARISONS = ("=", "==", "<>", "!=", "<", "<=", ">", ">=")
+
+
+def _plain_join_consumer(
+    stmt: X.SelectStmt, residual_where: Optional[X.Expr]
+) -> bool:
+    """True when all that follows the joins is a projection of plain
+    columns (no window, group-by, distinct or expression) and the WHERE
+    left after pushdown is absent or one comparison of columns and
+    numeric literals: the shape an engine's ``join_select`` takes."""
+    if stmt.distinct or stmt.group_by or stmt.having is not None:
+        return False
+    if len(stmt.columns) == 0 or not all(
+        isinstance(e, X.ColRef) for e, _ in stmt.columns
+    ):
+        return False
+    if residual_where is None:
+        return True
+    w = residual_where
+    if not isinstance(w, X.BinOp) or w.op not in _COMPARISONS:
+        return False
+    for side in (w.left, w.right):
+        if isinstance(side, X.ColRef):
+            continue
+        if (
+            isinstance(side, X.Lit)
+            and isinstance(side.value, (int, float))
+            and not isinstance(side.value, bool)
+        ):
+            continue
+        return False
+    return True
+
+
+def _join_with_consumer(
+    stmt: X.SelectStmt,
+    residual_where: Optional[X.Expr],
+    left: DataFrame,
+    right: DataFrame,
+    keys: List[str],
+    engine: Any,
+) -> Optional[DataFrame]:
+    """The last (inner) join together with the statement's projection and
+    residual WHERE through ``engine.join_select``; None when the engine
+    has no such entry point or declines the request, and the caller joins
+    and selects apart."""
+    join_select = getattr(engine, "join_select", None)
+    if join_select is None:
+        return None
+    from fugue_amd.dataframe.utils import get_join_schemas
+
+    _, schema = get_join_schemas(left, right, how="inner", on=keys)
+    where_expr = (
+        None
+        if residual_where is None
+        else _to_column_expr(residual_where, schema, {})
+    )
+    cols: List[ColumnExpr] = []
+    for e, alias in stmt.columns:
+        ce = _to_column_expr(e, schema, {})
+        cols.append(ce if alias is None else ce.alias(alias))
+    try:
+        return join_select(
+            left, right, "inner", keys, SelectColumns(*cols), where_expr
+        )
+    except NotImplementedError:
+        return None
+
+
 def _execute_core(
     stmt: X.SelectStmt, tables: Dict[str, DataFrame], engine: Any
 ) -> DataFrame:
@@ -705,6 +774,17 @@ def _execute_core(
                 f"join keys {keys} != common columns {common} "
                 "(fugue joins use all common columns)"
             )
+        if (
+            ji == len(stmt.joins) - 1
+            and how == "inner"
+            and _plain_join_consumer(stmt, residual_where)
+        ):
+            # the last join runs with its consumer when the engine offers it
+            fused = _join_with_consumer(
+                stmt, residual_where, res, right, keys, engine
+            )
+            if fused is not None:
+                return fused
         res = engine.join(res, right, how=how, on=keys if keys else None)
     # select columns
     schema = res.schema
