@@ -22,6 +22,12 @@ copy of the bytes it moves at the least (120 B/row: 24 for the forward
 summary, 40 for the forward apply, 8 for the backward summary, 48 for the
 backward apply).
 
+``--frame`` runs the framed case: a 7-row moving ``AVG`` (6 PRECEDING ..
+CURRENT ROW) plus a centred 7-row ``SUM`` (3 PRECEDING .. 3 FOLLOWING),
+``engine.frame_over`` on the ``seg_frame`` kernel against the same forced
+host path, and times each ``segmented_frame`` launch alone with device
+events.
+
 ``--kernels N`` instead runs only the kernels (and a plain copy of the
 bytes they move at the least: 33 B/row for the shift, 24 + 40 B/row for
 the scan's summary and apply) N times on the first shape, for a
@@ -57,6 +63,13 @@ _PARTITION_SQL = (
     "FIRST_VALUE(v) OVER (PARTITION BY k) AS f FROM df)"
 )
 _TOTAL_BYTES_PER_ROW = 120
+
+_FRAME_SQL = (
+    "SELECT k, v, AVG(v) OVER (PARTITION BY k ORDER BY v "
+    "ROWS BETWEEN 6 PRECEDING AND CURRENT ROW) AS m, "
+    "SUM(v) OVER (PARTITION BY k ORDER BY v "
+    "ROWS BETWEEN 3 PRECEDING AND 3 FOLLOWING) AS c FROM df"
+)
 
 
 def _step(engine, hdf, host: bool, sql: str = _SQL):
@@ -196,6 +209,66 @@ def _partition_case(engine, args, n: int, g: int) -> None:
     )
 
 
+def _frame_digest(res) -> tuple:
+    pdf = res.as_pandas()
+    return (
+        len(pdf), int(pdf["k"].sum()), float(pdf["m"].sum()),
+        int(pdf["m"].isna().sum()), float(pdf["c"].sum()),
+    )
+
+
+def _frame_case(engine, args, n: int, g: int) -> None:
+    hdf = _frame(engine, n, g)
+    before = engine.stats.get("window.device_frame")
+    for _ in range(args.warmup):
+        _, dres = _step(engine, hdf, False, _FRAME_SQL)
+    _, hres = _step(engine, hdf, True, _FRAME_SQL)
+    assert engine.stats.get("window.device_frame") == before + 2 * args.warmup
+    same = _frame_digest(dres) == _frame_digest(hres)
+    dev_ms, host_ms = [], []
+    for i in range(max(args.steps, args.host_steps)):
+        if i < args.steps:
+            dev_ms.append(_step(engine, hdf, False, _FRAME_SQL)[0])
+        if i < args.host_steps:
+            host_ms.append(_step(engine, hdf, True, _FRAME_SQL)[0])
+    pkeys, perm = engine._partition_sort(hdf, ["k"], ["v"], [True], "last")
+    c = hdf.col("v")
+    for _ in range(3):
+        dops.segmented_frame(perm, pkeys, c, "sum", -6, 0)
+    avg_ms = _event_ms(
+        lambda: dops.segmented_frame(perm, pkeys, c, "sum", -6, 0), 20
+    )
+    ctr_ms = _event_ms(
+        lambda: dops.segmented_frame(perm, pkeys, c, "sum", -3, 3), 20
+    )
+    d, h = float(np.median(dev_ms)), float(np.median(host_ms))
+    print(
+        json.dumps(
+            dict(
+                bench="window_frame_avg7_sum7",
+                rows=n,
+                groups=g,
+                device_ms=round(d, 3),
+                device_ms_min=round(min(dev_ms), 3),
+                device_ms_max=round(max(dev_ms), 3),
+                device_rows_per_s=round(n / d * 1e3),
+                host_ms=round(h, 3),
+                host_ms_min=round(min(host_ms), 3),
+                host_ms_max=round(max(host_ms), 3),
+                host_rows_per_s=round(n / h * 1e3),
+                host_over_device=round(h / d, 2),
+                results_equal=bool(same),
+                seg_frame_trailing7_ms=round(avg_ms, 4),
+                seg_frame_centred7_ms=round(ctr_ms, 4),
+                steps=args.steps,
+                host_steps=args.host_steps,
+                warmup=args.warmup,
+            )
+        ),
+        flush=True,
+    )
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="1000000,4000000,16000000")
@@ -205,6 +278,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kernels", type=int, default=0)
     ap.add_argument("--partition", action="store_true")
+    ap.add_argument("--frame", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("window_bench needs a GPU")
@@ -213,6 +287,11 @@ def main() -> None:
     groups = [int(x) for x in args.groups.split(",")]
     if args.kernels > 0:
         _kernels_only(engine, _frame(engine, rows[0], groups[0]), args.kernels)
+        return
+    if args.frame:
+        for n in rows:
+            for g in groups:
+                _frame_case(engine, args, n, g)
         return
     if args.partition:
         for n in rows:

@@ -1708,6 +1708,37 @@ std::vector<at::Tensor> seg_total(at::Tensor perm, at::Tensor pkeys,
   return {acc, cnt};
 }
 
+int64_t seg_frame_tile() { return SEG_FRAME_TILE; }
+int64_t seg_frame_max_reach() { return SEG_FRAME_MAX_REACH; }
+
+// SUM (op 0) / MIN (1) / MAX (2) / FIRST (3) / LAST (4) of the non-null
+// values in the frame [i + lo, i + hi] of every sorted position i,
+// clipped to its partition, and their count.  Returns (acc in the input
+// dtype, cnt int64) in original row order.  lo > hi is an empty frame.
+std::vector<at::Tensor> seg_frame(at::Tensor perm, at::Tensor pkeys,
+                                  at::Tensor data,
+                                  c10::optional<at::Tensor> valid, int64_t op,
+                                  int64_t lo, int64_t hi) {
+  seg_check_inputs(perm, pkeys);
+  int64_t n = perm.numel();
+  const uint8_t* vp = seg_check_value(data, valid, n);
+  TORCH_CHECK(op >= 0 && op <= 4, "op must be 0..4");
+  lo = lo > n ? n : (lo < -n ? -n : lo);
+  hi = hi > n ? n : (hi < -n ? -n : hi);
+  TORCH_CHECK(lo > hi || (lo < 0 ? -lo : 0) + (hi > 0 ? hi : 0) <=
+                             SEG_FRAME_MAX_REACH,
+              "frame reach beyond ", SEG_FRAME_MAX_REACH);
+  auto acc = at::empty_like(data);
+  auto cnt = at::empty({n}, perm.options());
+  if (n == 0) return {acc, cnt};
+  launch_seg_frame(perm.data_ptr<int64_t>(), pkeys.data_ptr<int64_t>(),
+                   reinterpret_cast<const int64_t*>(data.data_ptr()), vp, n,
+                   lo, hi, (int)op, data.is_floating_point() ? 1 : 0,
+                   reinterpret_cast<int64_t*>(acc.data_ptr()),
+                   cnt.data_ptr<int64_t>(), current_stream());
+  return {acc, cnt};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // limits the python layer plans by (ops.py keeps copies for hosts
   // without the extension; a GPU test compares them)
@@ -1828,6 +1859,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "segmented running sum/min/max + non-null count");
   m.def("seg_total", &seg_total,
         "whole-partition sum/min/max/first/last + non-null count");
+  m.def("seg_frame_tile", &seg_frame_tile,
+        "sorted positions per block of the frame kernel");
+  m.def("seg_frame_max_reach", &seg_frame_max_reach,
+        "largest frame reach the frame kernel takes");
+  m.def("seg_frame", &seg_frame,
+        "moving-frame sum/min/max/first/last + non-null count");
   m.def("gb_compact", &gb_compact,
         "deterministic group-table compaction");
   m.def("compact_columns_cap", &compact_columns_cap,

@@ -88,6 +88,13 @@ struct ExprProg {
 #define SEG_TOTAL_WORK(n) \
   (8 * (((int64_t)(n) + SEG_CHUNK - 1) / SEG_CHUNK) + 2 * (int64_t)(n))
 
+// seg_frame: sorted positions per block, and the largest frame reach
+// (positions before plus positions after the current row) it takes.  A
+// block stages SEG_FRAME_TILE + SEG_FRAME_MAX_REACH positions of 17 bytes
+// (key, value, validity) in LDS: 34 KiB, under the 64 KiB static limit.
+#define SEG_FRAME_TILE 1024
+#define SEG_FRAME_MAX_REACH 1024
+
 // top-k select: largest k, most stage-1 blocks (candidate rows = blocks * k)
 #define TOPK_MAX 16
 #define TOPK_BLOCKS 512
@@ -330,5 +337,13 @@ void launch_seg_total(const int64_t* perm, const int64_t* pkeys,
                       const int64_t* vals, const uint8_t* valid, int64_t n,
                       int op, int is_float, int64_t* work, int64_t* out_acc,
                       int64_t* out_cnt, hipStream_t stream);
+// op as launch_seg_total over the frame [i + lo, i + hi] of every sorted
+// position i, clipped to its partition; lo and hi are clamped to [-n, n]
+// and the reach max(0, -lo) + max(0, hi) must not exceed
+// SEG_FRAME_MAX_REACH (nothing is launched otherwise)
+void launch_seg_frame(const int64_t* perm, const int64_t* pkeys,
+                      const int64_t* vals, const uint8_t* valid, int64_t n,
+                      int64_t lo, int64_t hi, int op, int is_float,
+                      int64_t* out_acc, int64_t* out_cnt, hipStream_t stream);
 
 }  // extern "C"

@@ -526,7 +526,8 @@ __global__ __launch_bounds__(BLOCK) void seg_shift_kernel(
 #define SEG_OP_SUM 0
 #define SEG_OP_MIN 1
 #define SEG_OP_MAX 2
-// seg_total only: the first / last non-null value in sorted order
+// seg_total and seg_frame only: the first / last non-null value in sorted
+// order
 #define SEG_OP_FIRST 3
 #define SEG_OP_LAST 4
 
@@ -884,7 +885,95 @@ __global__ __launch_bounds__(BLOCK) void seg_total_apply_kernel(
   }
 }
 
+// ------------------------------------------------------------------ //
+// seg_frame: SUM/MIN/MAX/FIRST/LAST and COUNT over a moving ROWS frame  //
+//                                                                      //
+// Sorted position i of a partition folds the non-null values at sorted //
+// positions [i + lo, i + hi] that lie in its partition.  One block      //
+// handles a tile of SEG_FRAME_TILE positions: it gathers key, value     //
+// bits and validity of the tile and of a halo of max(0, -lo) positions //
+// before and max(0, hi) after it (clipped to [0, n)) into LDS, reading  //
+// perm coalesced, so the random gather through perm happens once per    //
+// staged position and not once per frame element.  Each lane then walks //
+// its positions' frames in ascending order from LDS; an element counts  //
+// when its key equals the row's (the precondition of seg_shift: equal   //
+// keys are contiguous) and it is valid.  Consecutive lanes read         //
+// consecutive words.  A sum starts from 0 and only ever adds, left to   //
+// right, fresh for every row: its bits depend on the frame alone.       //
+// ------------------------------------------------------------------ //
+
+#define SEG_FRAME_STAGE (SEG_FRAME_TILE + SEG_FRAME_MAX_REACH)
+
+__global__ __launch_bounds__(BLOCK) void seg_frame_kernel(
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ pkeys,
+    const int64_t* __restrict__ vals, const uint8_t* __restrict__ valid,
+    int64_t n, int lo, int hi, int op, int is_float,
+    int64_t* __restrict__ out_acc, int64_t* __restrict__ out_cnt) {
+  __shared__ int64_t s_key[SEG_FRAME_STAGE];
+  __shared__ int64_t s_val[SEG_FRAME_STAGE];
+  __shared__ uint8_t s_ok[SEG_FRAME_STAGE];
+  int64_t t0 = (int64_t)blockIdx.x * SEG_FRAME_TILE;
+  int64_t t1 = t0 + SEG_FRAME_TILE < n ? t0 + SEG_FRAME_TILE : n;
+  int64_t g0 = t0 - (lo < 0 ? -lo : 0);
+  int64_t g1 = t1 + (hi > 0 ? hi : 0);
+  if (g0 < 0) g0 = 0;
+  if (g1 > n) g1 = n;
+  // the launcher bounds the reach; a wider frame must not overrun LDS
+  if (g1 - g0 > SEG_FRAME_STAGE) return;  // block-uniform
+  int staged = (int)(g1 - g0);
+  for (int r = threadIdx.x; r < staged; r += BLOCK) {
+    int64_t j = seg_row(perm, g0 + r, n);
+    s_key[r] = pkeys[j];
+    s_val[r] = vals[j];
+    s_ok[r] = valid != nullptr ? (uint8_t)(valid[j] != 0) : (uint8_t)1;
+  }
+  __syncthreads();
+  for (int64_t i = t0 + threadIdx.x; i < t1; i += BLOCK) {
+    // frame clipped to the staged range [g0, g1): a holds a >= g0 and
+    // b < g1, so every r below is in [0, staged)
+    int64_t a = i + lo < g0 ? g0 : i + lo;
+    int64_t b = i + hi > g1 - 1 ? g1 - 1 : i + hi;
+    int64_t k = s_key[i - g0];
+    int64_t acc = 0, cnt = 0;
+    for (int64_t g = a; g <= b; ++g) {
+      int r = (int)(g - g0);
+      if (s_key[r] == k && s_ok[r]) {
+        int64_t v = s_val[r];
+        // 0 is the start of a sum (+0.0 as a double); the others take
+        // their first value as it is: no sentinels
+        acc = (cnt == 0 && op != SEG_OP_SUM) ? v
+                                             : seg_val_op(acc, v, op, is_float);
+        ++cnt;
+      }
+    }
+    int64_t j = seg_row(perm, i, n);
+    out_acc[j] = acc;
+    out_cnt[j] = cnt;
+  }
+}
+
 extern "C" {
+
+void launch_seg_frame(const int64_t* perm, const int64_t* pkeys,
+                      const int64_t* vals, const uint8_t* valid, int64_t n,
+                      int64_t lo, int64_t hi, int op, int is_float,
+                      int64_t* out_acc, int64_t* out_cnt,
+                      hipStream_t stream) {
+  if (n <= 0) return;
+  // beyond ±n nothing is in a frame; clamping keeps i + lo from overflowing
+  lo = lo > n ? n : (lo < -n ? -n : lo);
+  hi = hi > n ? n : (hi < -n ? -n : hi);
+  if (lo > hi) {  // every frame is empty: any such pair writes the zeros
+    lo = 1;
+    hi = 0;
+  }
+  int64_t reach = (lo < 0 ? -lo : 0) + (hi > 0 ? hi : 0);
+  if (reach > SEG_FRAME_MAX_REACH) return;  // the binding refuses these
+  int64_t nblocks = (n + SEG_FRAME_TILE - 1) / SEG_FRAME_TILE;
+  hipLaunchKernelGGL(seg_frame_kernel, dim3((unsigned)nblocks), dim3(BLOCK), 0,
+                     stream, perm, pkeys, vals, valid, n, (int)lo, (int)hi, op,
+                     is_float, out_acc, out_cnt);
+}
 
 void launch_seg_shift(const int64_t* perm, const int64_t* pkeys,
                       const int64_t* vals, const uint8_t* valid, int64_t n,

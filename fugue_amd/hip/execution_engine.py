@@ -2192,6 +2192,198 @@ class HipExecutionEngine(ExecutionEngine):
             self._stats.add("window.device_partition")
         return HipDataFrame.from_columns(cols, schema, self._device)
 
+    def _check_frame_items(self, d: HipDataFrame, items: List[Any]) -> bool:
+        """Checks of ``frame_over`` that read the schema and the arguments
+        only.  Returns whether some item reads an integer column (see
+        ``_check_value_items``)."""
+        names = set()
+        any_int = False
+        for name, func, arg, lo, hi in items:
+            if func not in self._PARTITION_WINDOW_FUNCS:
+                raise NotImplementedError(f"window function {func}")
+            if name in d.schema or name in names:
+                raise NotImplementedError(f"column {name} already exists")
+            names.add(name)
+            for bound in (lo, hi):
+                if bound is not None and (
+                    isinstance(bound, bool) or not isinstance(bound, int)
+                ):
+                    raise NotImplementedError("frame bound not an integer")
+            if lo is None or hi is None:
+                if (lo, hi) == (None, 0):
+                    if func in ("first_value", "last_value"):
+                        raise NotImplementedError(
+                            f"running {func} stays on the host"
+                        )
+                elif (lo, hi) != (None, None):
+                    raise NotImplementedError(
+                        "half-unbounded frame stays on the host"
+                    )
+            elif lo <= hi and (
+                max(0, -lo) + max(0, hi) > dops.SEG_FRAME_MAX_REACH
+            ):
+                # decided on the written bounds, not on the shard's row
+                # count, so every rank of a distributed run agrees
+                raise NotImplementedError("frame reach beyond the kernel's")
+            if arg is None:
+                if func != "count":
+                    raise NotImplementedError(f"{func} needs an argument")
+                continue
+            if arg not in d.schema:
+                raise NotImplementedError(f"column {arg} not in the frame")
+            tp = d.schema[arg].type
+            is_int = pa.types.is_signed_integer(tp)
+            if not (is_int or pa.types.is_floating(tp)) or isinstance(
+                d.col(arg), StringDeviceColumn
+            ):
+                # strings, nested, bool, dates: the host's types differ
+                raise NotImplementedError(f"window over a {tp} column")
+            any_int |= is_int
+        return any_int
+
+    def frame_over(
+        self,
+        df: DataFrame,
+        partition_by: List[str],
+        order_by: List[Tuple[str, bool]],
+        items: List[Tuple[str, str, Optional[str], Optional[int], Optional[int]]],
+    ) -> DataFrame:
+        """``df`` plus one framed window column per item, all over
+        (PARTITION BY ``partition_by`` ORDER BY ``order_by``); nulls sort
+        last and ties keep original row order (so does every row when
+        ``order_by`` is empty).  Each item is ``(name, func, arg_column,
+        lo, hi)`` with ``func`` in ``sum`` / ``min`` / ``max`` / ``count``
+        / ``avg`` / ``first_value`` / ``last_value`` and the frame ROWS
+        BETWEEN ``lo`` AND ``hi`` as signed row offsets from the current
+        row, None for an unbounded side; ``count`` with
+        ``arg_column=None`` is ``COUNT(*)``.  Nulls and NaN are skipped,
+        counts are never null and every other function is null when its
+        frame holds no value.  Values and types are the host SQL
+        executor's (table in ``sql/planner.py``).  Bounded frames run on
+        ``segmented_frame``, ``(None, 0)`` on ``segmented_scan`` and
+        ``(None, None)`` on ``segmented_total``.  Raises
+        ``NotImplementedError`` for shapes that stay on the host."""
+        d = self.to_df(df)
+        if not isinstance(d, HipDataFrame):
+            raise NotImplementedError("frame_over needs a device frame")
+        if os.environ.get("FUGUE_HIP_FORCE_HOST_WINDOW", "") == "1":
+            # A/B probe (benchmarks/window_bench.py): the host path
+            raise NotImplementedError("host window forced")
+        if len(partition_by) == 0:
+            raise NotImplementedError("window without PARTITION BY")
+        if len(items) == 0:
+            raise NotImplementedError("no window items")
+        order_names = [c for c, _ in order_by]
+        order_asc = [bool(a) for _, a in order_by]
+        keys = list(partition_by)
+        items = [tuple(it) for it in items]
+        any_int = self._check_frame_items(d, items)
+        self._check_rank_shape(d, keys, order_names)
+        if any_int:
+            # as in window_over: an integer column under a validity mask
+            # reaches the host as another type; the ranks decide together
+            masked = int(
+                any(
+                    it[2] is not None
+                    and pa.types.is_integer(d.schema[it[2]].type)
+                    and d.col(it[2]).valid is not None
+                    for it in items
+                )
+            )
+            if self.is_distributed:
+                masked = int(self._comm.allreduce_sum(masked))
+            if masked > 0:
+                raise NotImplementedError("nullable integer window column")
+        total = d.count()
+        if self.is_distributed:
+            total = int(self._comm.allreduce_sum(total))
+        if total == 0:
+            # the host executor types an empty window column as double
+            raise NotImplementedError("window over an empty frame")
+        new_cols: Dict[str, DeviceColumn] = {}
+        with op_range("fugue.window.frame"):
+            if self.is_distributed:
+                d = self._shuffle_by_columns(d, keys)
+            pkeys, perm = self._partition_sort(
+                d, keys, order_names, order_asc, "last"
+            )
+            done: Dict[Tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+            def _fold(
+                arg: Optional[str],
+                op: str,
+                lo: Optional[int],
+                hi: Optional[int],
+                as_double: bool = False,
+            ) -> Tuple[torch.Tensor, torch.Tensor]:
+                key = (arg, op, lo, hi, as_double)
+                if key not in done:
+                    col: Any
+                    if arg is None:  # COUNT(*): every row counts
+                        col = (torch.ones_like(pkeys), None)
+                    elif as_double:
+                        c = d.col(arg)
+                        col = (c.data.to(torch.float64), c.valid)
+                    else:
+                        col = d.col(arg)
+                    if lo is not None and hi is not None:
+                        done[key] = dops.segmented_frame(
+                            perm, pkeys, col, op, lo, hi
+                        )
+                    elif hi is None:
+                        done[key] = dops.segmented_total(perm, pkeys, col, op)
+                    else:
+                        done[key] = dops.segmented_scan(perm, pkeys, col, op)
+                return done[key]
+
+            def _any_count(
+                arg: Optional[str], lo: Optional[int], hi: Optional[int]
+            ) -> torch.Tensor:
+                # the count comes with every fold: take one that exists
+                for (a, _o, l, h, _f), (_acc, cnt) in done.items():
+                    if a == arg and l == lo and h == hi:
+                        return cnt
+                return _fold(arg, "sum", lo, hi)[1]
+
+            for name, func, arg, lo, hi in items:
+                if func == "count":
+                    if arg is None and (lo, hi) == (None, 0):
+                        cnt = dops.segmented_rank(perm, pkeys, [], "row_number")
+                    else:
+                        cnt = _any_count(arg, lo, hi)
+                    new_cols[name] = DeviceColumn(cnt, None, pa.int64())
+                    continue
+                if func == "avg":
+                    acc, cnt = _fold(arg, "sum", lo, hi, as_double=True)
+                    some = cnt > 0
+                    mean = acc / torch.where(some, cnt, torch.ones_like(cnt))
+                    new_cols[name] = DeviceColumn(mean, some, pa.float64())
+                    continue
+                op = {"first_value": "first", "last_value": "last"}.get(
+                    func, func
+                )
+                acc, cnt = _fold(arg, op, lo, hi)
+                # long only when no frame can be empty: the column is
+                # null-free here and the frame holds the current row
+                if (
+                    not acc.is_floating_point()
+                    and (lo is None or lo <= 0)
+                    and (hi is None or hi >= 0)
+                ):
+                    new_cols[name] = DeviceColumn(acc, None, pa.int64())
+                else:
+                    new_cols[name] = DeviceColumn(
+                        acc.to(torch.float64), cnt > 0, pa.float64()
+                    )
+        cols = dict(d.columns_map)
+        cols.update(new_cols)
+        schema = d.schema + Schema(
+            [(n, c.pa_type) for n, c in new_cols.items()]
+        )
+        for _ in items:
+            self._stats.add("window.device_frame")
+        return HipDataFrame.from_columns(cols, schema, self._device)
+
     # ------------------------------------------------------------------ #
     # select / aggregate: device fast path                                 #
     # ------------------------------------------------------------------ #

@@ -2104,6 +2104,103 @@ def segmented_total(
     return acc, cnt
 
 
+# Largest frame reach seg_frame takes: a copy of SEG_FRAME_MAX_REACH in
+# csrc/relational.h for hosts without the extension (a GPU test compares
+# the two).
+SEG_FRAME_MAX_REACH = 1024
+
+
+def _segmented_frame_cpu(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    data: torch.Tensor,
+    valid: Optional[torch.Tensor],
+    op: int,
+    lo: int,
+    hi: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(acc, cnt) per SORTED position: one pass per offset from ``lo`` to
+    ``hi``, each folding the value ``d`` positions away where that row is
+    in the same partition and non-null.  A sum therefore adds its frame
+    left to right, starting from 0."""
+    n = perm.numel()
+    ks = pkeys.index_select(0, perm)
+    xs = data.index_select(0, perm)
+    if valid is not None:
+        ok = valid.index_select(0, perm)
+    else:
+        ok = torch.ones(n, dtype=torch.bool)
+    acc = torch.zeros_like(xs)
+    cnt = torch.zeros(n, dtype=torch.int64)
+    for d in range(lo, hi + 1):
+        if abs(d) >= n:
+            continue
+        dst = slice(0, n - d) if d >= 0 else slice(-d, n)
+        src = slice(d, n) if d >= 0 else slice(0, n + d)
+        take = (ks[src] == ks[dst]) & ok[src]
+        x, a, c = xs[src], acc[dst], cnt[dst]
+        if op == 0:
+            new = a + x  # int64 wraps like the unsigned device add
+        elif op == 1:
+            new = torch.where((c == 0) | (x < a), x, a)
+        elif op == 2:
+            new = torch.where((c == 0) | (x > a), x, a)
+        elif op == 3:
+            new = torch.where(c == 0, x, a)
+        else:
+            new = x
+        acc[dst] = torch.where(take, new, a)
+        cnt[dst] = c + take.to(torch.int64)
+    return acc, cnt
+
+
+def segmented_frame(
+    perm: torch.Tensor,
+    pkeys: torch.Tensor,
+    col: Any,
+    func: str,
+    lo: int,
+    hi: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``sum`` / ``min`` / ``max`` / ``first`` / ``last`` of one value
+    column over the moving frame ROWS BETWEEN ``lo`` AND ``hi``: signed
+    offsets in sorted positions from the row itself (``-2`` is 2
+    PRECEDING), clipped to the row's partition; ``lo > hi`` is legal and
+    leaves every frame empty.  Returns ``(acc, cnt)`` in ORIGINAL row
+    order: ``cnt`` (int64) is the number of non-null values in the row's
+    frame and ``acc`` (int64 or float64) their aggregate, 0 when ``cnt``
+    is 0.  A sum starts from 0 and adds the frame's values in sorted
+    order, fresh for every row, so the CPU and the device form agree bit
+    for bit; integer sums wrap.  ``first`` / ``last`` are the first /
+    last non-null value of the frame.  Inputs as :func:`segmented_scan`.
+    Offsets are clamped to ``[-n, n]``.  A frame whose reach ``max(0,
+    -lo) + max(0, hi)`` then exceeds ``SEG_FRAME_MAX_REACH`` raises
+    ``NotImplementedError`` (unless it is empty for every row)."""
+    if func not in TOTAL_FUNCS:
+        raise ValueError(f"unknown frame function {func!r}")
+    op = TOTAL_FUNCS[func]
+    data, valid = _value_col_parts(col)
+    perm = perm.contiguous()
+    pkeys = pkeys.contiguous()
+    n = perm.numel()
+    lo = max(-n, min(n, int(lo)))  # beyond ±n nothing is in the frame
+    hi = max(-n, min(n, int(hi)))
+    if n == 0 or lo > hi or lo >= n or hi <= -n:
+        # no row has anything in its frame
+        return torch.zeros_like(data), torch.zeros_like(perm)
+    if max(0, -lo) + max(0, hi) > SEG_FRAME_MAX_REACH:
+        raise NotImplementedError("window frame reach beyond the kernel's")
+    if _is_cpu(perm):
+        acc = torch.empty_like(data)
+        cnt = torch.empty(n, dtype=torch.int64)
+        a, c = _segmented_frame_cpu(perm, pkeys, data, valid, op, lo, hi)
+        acc[perm] = a
+        cnt[perm] = c
+        return acc, cnt
+    acc, cnt = get_ext().seg_frame(perm, pkeys, data, valid, op, lo, hi)
+    return acc, cnt
+
+
 def take_per_group_indices(
     perm: torch.Tensor, pkeys: torch.Tensor, n: int
 ) -> torch.Tensor:

@@ -264,17 +264,25 @@ class WindowFunc(Expr):
     Implemented in the executor itself (the reference delegates window
     functions to its SQL backends, e.g. duckdb/spark).  With ORDER BY,
     aggregate windows are cumulative (ROWS UNBOUNDED PRECEDING..CURRENT
-    ROW); without, they span the whole partition."""
+    ROW); without, they span the whole partition.
+
+    ``frame`` is the explicit ``ROWS`` frame ``(lo, hi)``: signed row
+    offsets from the current row (``n PRECEDING`` is ``-n``), None for an
+    unbounded side; ``frame is None`` means no frame was written.  A
+    framed aggregate has plain SQL null semantics (``_eval_frame``); the
+    unframed ones above keep their pandas ones."""
 
     def __init__(
         self,
         func: "FuncCall",
         partition_by: List[Expr],
         order_by: List["OrderItem"],
+        frame: Optional[Tuple[Optional[int], Optional[int]]] = None,
     ):
         self.func = func
         self.partition_by = partition_by
         self.order_by = order_by
+        self.frame = frame
 
     @property
     def is_agg(self) -> bool:
@@ -331,6 +339,9 @@ class WindowFunc(Expr):
             kind="stable",
         )
         g = sorted_w.groupby(pcols, sort=False, dropna=False)
+        if self.frame is not None:
+            res = self._eval_frame(sorted_w, g, fname, val)
+            return pd.Series(res, index=sorted_w.index).sort_index()
         rn = g.cumcount() + 1
         if fname == "ROW_NUMBER":
             res = rn
@@ -406,6 +417,138 @@ class WindowFunc(Expr):
         else:
             raise NotImplementedError(f"window function {fname}")
         return pd.Series(res, index=sorted_w.index).sort_index()
+
+    _FRAME_FUNCS = {
+        "SUM": "sum", "MIN": "min", "MAX": "max", "COUNT": "count",
+        "AVG": "avg", "MEAN": "avg",
+        "FIRST_VALUE": "first", "FIRST": "first",
+        "LAST_VALUE": "last", "LAST": "last",
+    }
+
+    def _eval_frame(
+        self, sorted_w: pd.DataFrame, g: Any, fname: str,
+        val: Optional[pd.Series],
+    ) -> Any:
+        """The framed aggregate per SORTED position.  Position ``i`` of a
+        partition at sorted positions ``[s, e)`` sees the rows
+        ``[max(s, i+lo), min(e-1, i+hi)]``.  Nulls (NaN included) are
+        skipped; COUNT is never null, everything else is null when the
+        frame holds no value.  SUM/MIN/MAX/FIRST/LAST of a plain signed
+        integer column under a frame that always holds the current row
+        are long (SUM wraps); otherwise they are double, integers being
+        computed in int64 and converted at the end.  A bounded double SUM
+        starts from +0.0 and adds the frame's values left to right, fresh
+        for every row: one vectorised pass per offset."""
+        import numpy as np
+
+        func = self._FRAME_FUNCS.get(fname)
+        if func is None:
+            raise NotImplementedError(f"window function {fname} with a frame")
+        if val is None and func != "count":
+            raise SyntaxError(f"{fname} requires an argument")
+        lo, hi = self.frame  # type: ignore
+        n = len(sorted_w)
+        pos = np.arange(n, dtype=np.int64)
+        pid = g.ngroup().to_numpy()
+        head = np.ones(n, dtype=bool)
+        head[1:] = pid[1:] != pid[:-1]
+        tail = np.ones(n, dtype=bool)
+        tail[:-1] = head[1:]
+        s = np.maximum.accumulate(np.where(head, pos, 0))
+        e1 = np.minimum.accumulate(np.where(tail, pos, n - 1)[::-1])[::-1]
+        a = s if lo is None else np.maximum(s, pos + max(-n, min(n, lo)))
+        b = e1 if hi is None else np.minimum(e1, pos + max(-n, min(n, hi)))
+        empty = a > b
+        ac = np.clip(a, 0, n - 1)
+        bc = np.clip(b, 0, n - 1)
+        if val is None:
+            ok = np.ones(n, dtype=bool)
+        else:
+            v = sorted_w["__v"]
+            if v.dtype == object:
+                try:
+                    v = pd.to_numeric(v)
+                except (ValueError, TypeError):
+                    pass
+            ok = v.notna().to_numpy()
+        csum = np.concatenate([[0], np.cumsum(ok, dtype=np.int64)])
+        cnt = np.where(empty, 0, csum[bc + 1] - csum[ac])
+        if func == "count":
+            return cnt
+        some = cnt > 0
+        numeric = pd.api.types.is_numeric_dtype(v.dtype)
+        if not numeric and func not in ("first", "last"):
+            raise NotImplementedError(
+                f"{fname} over a frame of a {v.dtype} column"
+            )
+        is_int = pd.api.types.is_signed_integer_dtype(v.dtype)
+        long_result = (
+            isinstance(v.dtype, np.dtype)
+            and v.dtype.kind == "i"
+            and (lo is None or lo <= 0)
+            and (hi is None or hi >= 0)
+        )
+        if not numeric:
+            x = v.to_numpy(dtype=object)
+        elif is_int and func != "avg":
+            x = v.to_numpy(dtype="int64", na_value=0)
+        else:
+            x = v.to_numpy(dtype="float64", na_value=np.nan)
+            x = np.where(ok, x, 0.0)  # +0.0 stands in for a skipped null
+        if func in ("first", "last"):
+            if func == "first":  # the next non-null at or after a
+                nxt = np.minimum.accumulate(np.where(ok, pos, n)[::-1])[::-1]
+                idx = nxt[ac]
+            else:  # the last non-null at or before b
+                idx = np.maximum.accumulate(np.where(ok, pos, -1))[bc]
+            acc = x[np.where(some, idx, 0)]
+            if not numeric:
+                acc[~some] = None
+                return acc
+        elif lo is not None and hi is not None:
+            longest = int((e1 - s).max()) + 1
+            acc = np.zeros(n, dtype=x.dtype)
+            seen = np.zeros(n, dtype=bool)
+            for d in range(max(lo, -longest), min(hi, longest) + 1):
+                src = pos + d
+                inside = (src >= s) & (src <= e1)
+                srcc = np.where(inside, src, pos)
+                take = inside & ok[srcc]
+                xs = x[srcc]
+                if func in ("sum", "avg"):
+                    acc = np.where(take, acc + xs, acc)
+                else:
+                    better = xs < acc if func == "min" else xs > acc
+                    acc = np.where(take & (~seen | better), xs, acc)
+                    seen |= take
+        else:
+            # an unbounded side: the per-partition cumulative form, read
+            # at the clipped other end (forward from s, or backward from
+            # the partition's last row)
+            fwd = lo is None
+            at = bc if fwd else ac
+            order = slice(None) if fwd else slice(None, None, -1)
+            keys = pid[order]
+            if func in ("sum", "avg"):
+                cum = pd.Series(x[order]).groupby(keys, sort=False).cumsum()
+            else:
+                # a null becomes the identity of MIN/MAX; whether the
+                # result is null is decided by cnt, never by this value
+                if x.dtype.kind == "f":
+                    ident = np.inf if func == "min" else -np.inf
+                else:
+                    info = np.iinfo(np.int64)
+                    ident = info.max if func == "min" else info.min
+                gs = pd.Series(np.where(ok, x, ident)[order]).groupby(
+                    keys, sort=False
+                )
+                cum = gs.cummin() if func == "min" else gs.cummax()
+            acc = cum.to_numpy()[order][at]
+        if func == "avg":
+            return np.where(some, acc / np.where(some, cnt, 1), np.nan)
+        if long_result:
+            return acc
+        return np.where(some, acc.astype("float64"), np.nan)
 
 
 class Case(Expr):
@@ -939,6 +1082,57 @@ def _parse_unary(ts: TokenStream) -> Expr:
     return _parse_primary(ts)
 
 
+_UNFRAMED_WINDOW_FUNCS = ("ROW_NUMBER", "RANK", "DENSE_RANK", "LAG", "LEAD")
+
+
+def _parse_frame_bound(ts: TokenStream) -> Tuple[int, Optional[int]]:
+    """One ``ROWS`` frame bound as (kind, offset): kind 0 PRECEDING,
+    1 CURRENT ROW, 2 FOLLOWING; the offset is signed and relative to the
+    current row, None when UNBOUNDED."""
+    if ts.take_kw("CURRENT"):
+        ts.expect_kw("ROW")
+        return 1, 0
+    n: Optional[int] = None
+    if not ts.take_kw("UNBOUNDED"):
+        t = ts.peek()
+        if t is None or t.kind != "NUMBER" or not t.value.isdigit():
+            raise SyntaxError(
+                "frame bound must be UNBOUNDED, CURRENT ROW or a "
+                f"non-negative integer, got {t.value if t else 'EOF'}"
+            )
+        ts.next()
+        n = int(t.value)
+    if ts.take_kw("PRECEDING"):
+        return 0, (None if n is None else -n)
+    if ts.take_kw("FOLLOWING"):
+        return 2, n
+    t = ts.peek()
+    raise SyntaxError(
+        f"expected PRECEDING or FOLLOWING, got {t.value if t else 'EOF'}"
+    )
+
+
+def _parse_rows_frame(
+    ts: TokenStream,
+) -> Tuple[Optional[int], Optional[int]]:
+    """The frame after ``ROWS``: ``(lo, hi)`` as signed row offsets from
+    the current row, None for an unbounded side."""
+    if ts.take_kw("BETWEEN"):
+        lo_kind, lo = _parse_frame_bound(ts)
+        ts.expect_kw("AND")
+        hi_kind, hi = _parse_frame_bound(ts)
+    else:
+        lo_kind, lo = _parse_frame_bound(ts)
+        hi_kind, hi = 1, 0
+    if lo is None and lo_kind == 2:
+        raise SyntaxError("frame start cannot be UNBOUNDED FOLLOWING")
+    if hi is None and hi_kind == 0:
+        raise SyntaxError("frame end cannot be UNBOUNDED PRECEDING")
+    if lo_kind > hi_kind:
+        raise SyntaxError("frame start bound comes after its end bound")
+    return lo, hi
+
+
 def _parse_primary(ts: TokenStream) -> Expr:
     t = ts.peek()
     if t is None:
@@ -1050,13 +1244,20 @@ def _parse_primary(ts: TokenStream) -> Expr:
                             break
                 nt = ts.peek()
                 if nt is not None and nt.kind == "NAME" and nt.upper in (
-                    "ROWS", "RANGE", "GROUPS",
+                    "RANGE", "GROUPS",
                 ):
                     raise NotImplementedError(
-                        "explicit window frame specs are not supported"
+                        f"{nt.upper} window frame specs are not supported"
                     )
+                frame: Optional[Tuple[Optional[int], Optional[int]]] = None
+                if ts.take_kw("ROWS"):
+                    frame = _parse_rows_frame(ts)
+                    if name.upper() in _UNFRAMED_WINDOW_FUNCS:
+                        raise SyntaxError(
+                            f"{name.upper()} does not take a window frame"
+                        )
                 ts.expect_punct(")")
-                return WindowFunc(fc, partition_by, order_by)
+                return WindowFunc(fc, partition_by, order_by, frame)
             return fc
         # qualified / unqualified column, or alias.*
         name = ts.next().value

@@ -514,6 +514,84 @@ def _find_partition_windows(
     return over[0], over[1], items
 
 
+# Framed windows (an explicit ``ROWS`` frame) the engine computes with its
+# segmented frame kernel, or with the scan / total kernels where the frame
+# is one of theirs (``engine.frame_over``).  They have plain SQL null
+# semantics, not the pandas ones of the unframed forms above: nulls are
+# skipped, COUNT is never null and everything else is null exactly when
+# the frame holds no value.  Result types of ``executor.WindowFunc.
+# _eval_frame``; they depend on the column type and the frame shape only,
+# never on the data:
+#
+#   function                   null-free byte,short,int,long       double,
+#                              frame always    frame that can      float
+#                              holds the row   be empty
+#   SUM MIN MAX                long            double              double
+#   FIRST_/LAST_VALUE          long            double              double
+#   COUNT(x) COUNT(*)          long            long                long
+#   AVG(x)                     double          double              double
+#
+# A frame always holds the current row when lo <= 0 <= hi (an unbounded
+# side counts as satisfied).  Integers are computed in int64 (SUM wraps)
+# and converted at the end; float is widened to double before anything is
+# added.  An integer column that carries nulls reaches the executor as
+# another series type (double results): ``frame_over`` declines it, as it
+# does strings, bools, dates, the half-unbounded frames other than
+# UNBOUNDED PRECEDING..CURRENT ROW and a reach beyond the kernel's, and
+# the statement falls back.
+_FRAME_WINDOWS = dict(_PARTITION_WINDOWS, **_PARTITION_ORDERED_WINDOWS)
+
+
+def _find_frame_windows(
+    stmt: X.SelectStmt, schema: Schema
+) -> Optional[Tuple[List[str], List[Tuple[str, bool]], Dict[int, Tuple]]]:
+    """(partition columns, order (column, asc) pairs, {select index:
+    ``frame_over`` item}) when every window item of the statement carries
+    a ``ROWS`` frame, all share one OVER clause (the frames may differ)
+    and the statement has the plain shape the lowering needs.  None when
+    no window item carries a frame: the other lowerings look at the
+    statement next.  Raises UnsupportedPlan for every other statement
+    with a framed item, so none of them ever sees one."""
+    found = [
+        i for i, (e, _a) in enumerate(stmt.columns)
+        if isinstance(e, X.WindowFunc)
+    ]
+    if not any(stmt.columns[i][0].frame is not None for i in found):
+        return None
+    if stmt.group_by or stmt.having is not None or stmt.distinct:
+        raise UnsupportedPlan("window with GROUP BY/HAVING/DISTINCT")
+    if stmt.joins:
+        raise UnsupportedPlan("window over a join")
+    over: Optional[Tuple[List[str], List[Tuple[str, bool]]]] = None
+    items: Dict[int, Tuple] = {}
+    for i in found:
+        w = stmt.columns[i][0]
+        if w.frame is None:
+            raise UnsupportedPlan("framed and unframed window items")
+        func = _FRAME_WINDOWS.get(w.func.name)
+        if func is None or w.func.distinct or len(w.func.args) != 1:
+            raise UnsupportedPlan(f"framed window function {w.func.name}")
+        this = _window_over_clause(w, schema)
+        if over is not None and this != over:
+            raise UnsupportedPlan("window items with different OVER clauses")
+        over = this
+        arg: Optional[str] = None
+        a0 = w.func.args[0]
+        if isinstance(a0, X.Star):
+            if func != "count":
+                raise UnsupportedPlan(f"{w.func.name}(*)")
+        elif isinstance(a0, X.ColRef) and a0.name in schema:
+            arg = a0.name
+        else:
+            raise UnsupportedPlan("window argument expression")
+        name = f"{_VALUE_TMP}{i}"
+        if name in schema:
+            raise UnsupportedPlan("reserved column name in input")
+        items[i] = (name, func, arg, w.frame[0], w.frame[1])
+    assert over is not None
+    return over[0], over[1], items
+
+
 def _find_value_windows(
     stmt: X.SelectStmt, schema: Schema
 ) -> Optional[Tuple[List[str], List[Tuple[str, bool]], Dict[int, Tuple]]]:
@@ -794,13 +872,27 @@ def _execute_core(
     cols: List[ColumnExpr] = []
     from fugue_amd.column.expressions import all_cols
 
-    partition_windows = _find_partition_windows(stmt, schema)
+    frame_windows = _find_frame_windows(stmt, schema)
+    partition_windows = None
+    if frame_windows is None:
+        partition_windows = _find_partition_windows(stmt, schema)
     value_windows = None
-    if partition_windows is None:
+    if frame_windows is None and partition_windows is None:
         value_windows = _find_value_windows(stmt, schema)
     value_items: Dict[int, Tuple] = {}
     window = None
-    if partition_windows is not None:
+    if frame_windows is not None:
+        # WHERE filters the rows the windows see, so it runs first
+        if where_expr is not None:
+            res = engine.select(
+                res, SelectColumns(all_cols()), where=where_expr
+            )
+            where_expr = None
+        pcols, ocols, value_items = frame_windows
+        res = engine.frame_over(
+            res, pcols, ocols, [value_items[i] for i in sorted(value_items)]
+        )
+    elif partition_windows is not None:
         # WHERE filters the rows the windows see, so it runs first
         if where_expr is not None:
             res = engine.select(
