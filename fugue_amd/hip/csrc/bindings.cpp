@@ -772,16 +772,27 @@ at::Tensor scatter_tile_compact(at::Tensor vals, at::Tensor rank,
   return out;
 }
 
-// gb_dense_aggregate_binned over the 16-bit ids of the compact layout
+// gb_dense_aggregate_binned over the 16-bit ids of the compact layout.
+// With `out` (contiguous fp64, at least n_groups long) the sums are ADDED
+// to its first n_groups elements and that view is returned.
 at::Tensor gb_dense_aggregate_compact(at::Tensor rel, at::Tensor pvals,
                                       at::Tensor bin_offsets,
                                       at::Tensor bin_group_base,
                                       at::Tensor bin_chunk_base,
                                       int64_t total_chunks, int64_t n_groups,
-                                      int64_t chunk, int64_t slots) {
+                                      int64_t chunk, int64_t slots,
+                                      c10::optional<at::Tensor> out_opt) {
   TORCH_CHECK(n_groups >= 0 && n_groups < (int64_t(1) << 31),
               "n_groups must fit int32");
-  auto out_sum = at::zeros({n_groups}, pvals.options());
+  if (out_opt.has_value()) {
+    check_gpu(*out_opt, "out");
+    TORCH_CHECK(out_opt->scalar_type() == at::kDouble &&
+                    out_opt->is_contiguous() && out_opt->dim() == 1 &&
+                    out_opt->numel() >= n_groups,
+                "out must be contiguous fp64 of at least n_groups");
+  }
+  auto out_sum = out_opt.has_value() ? out_opt->narrow(0, 0, n_groups)
+                                     : at::zeros({n_groups}, pvals.options());
   dense_aggregate_compact_into(rel, pvals, bin_offsets, bin_group_base,
                                bin_chunk_base, total_chunks, chunk, slots,
                                out_sum);
@@ -920,9 +931,15 @@ void jsel_operand(const py::handle& spec, int s, int64_t np, int64_t nb,
 // output columns at probe length (capacity mode) followed by the cursor
 // [1]: the caller narrows to its value.  Row order is not defined.  An
 // empty probe or build side returns empty columns without a launch.
+// block_rows forces the probe rows per block (tests); 0 is by probe length.
 std::vector<at::Tensor> join_unique_select(
     at::Tensor pkeys, at::Tensor bkeys, at::Tensor heads, at::Tensor next,
-    py::object pred, std::vector<std::pair<int64_t, at::Tensor>> out_specs) {
+    py::object pred, std::vector<std::pair<int64_t, at::Tensor>> out_specs,
+    int64_t block_rows) {
+  TORCH_CHECK(block_rows == 0 || block_rows == 1024 || block_rows == 2048 ||
+                  block_rows == COMPACT_CHUNK,
+              "block_rows is 0 (by probe length), 1024, 2048 or ",
+              COMPACT_CHUNK);
   check_gpu(pkeys, "probe_keys");
   check_gpu(bkeys, "build_keys");
   check_gpu(heads, "heads");
@@ -978,7 +995,7 @@ std::vector<at::Tensor> join_unique_select(
     launch_join_unique_select(
         pkeys.data_ptr<int64_t>(), np, bkeys.data_ptr<int64_t>(),
         heads.data_ptr<int32_t>(), next.data_ptr<int32_t>(), tsize, &p, &c,
-        cursor.data_ptr<int64_t>(), current_stream());
+        cursor.data_ptr<int64_t>(), (int)block_rows, current_stream());
   }
   outs.push_back(cursor);
   return outs;
@@ -1815,7 +1832,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sum per group over the binned layout, 16-bit ids", py::arg("rel"),
         py::arg("pvals"), py::arg("bin_offsets"), py::arg("bin_group_base"),
         py::arg("bin_chunk_base"), py::arg("total_chunks"),
-        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"));
+        py::arg("n_groups"), py::arg("chunk"), py::arg("slots"),
+        py::arg("out") = py::none());
   m.def("gb_replay_compact", &gb_replay_compact,
         "replayed step over the compact binned layout: scatter + aggregate",
         py::arg("vals"), py::arg("rel"), py::arg("rank"),
@@ -1829,7 +1847,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("join_unique_select", &join_unique_select,
         "unique inner join + residual comparison + projection, one pass",
         py::arg("probe_keys"), py::arg("build_keys"), py::arg("heads"),
-        py::arg("next"), py::arg("pred"), py::arg("out_specs"));
+        py::arg("next"), py::arg("pred"), py::arg("out_specs"),
+        py::arg("block_rows") = 0);
   m.def("join_emit_unique", &join_emit_unique,
         "single-pass join emit for unique build keys");
   m.def("hash_string_column", &hash_string_column,

@@ -636,6 +636,17 @@ __global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_binned_kernel(
 // and a row costs 10 bytes instead of 12.  A rel past the table (a bin
 // wider than SLOTS) adds straight to out_sum[base + rel], as there.  rel
 // and part_vals are 16-byte aligned at row 0 (whole allocations).
+//
+// A block owns a contiguous range of virtual chunks, total_chunks split
+// evenly over the grid (sizes differ by at most one), and walks it bin by
+// bin: the chunks of one bin in the range are ONE row interval, so the
+// table is carried across them and flushed (and zeroed again) only where
+// the bin changes and at the end of the range.  The row loop over an
+// interval is software-pipelined with two register sets of one four-row
+// group per lane: the next set's loads are issued before the current
+// set's LDS adds.  Loads are unconditional off clamped indices; a group
+// past the interval is dropped when it is consumed.  No block waits on
+// another; every loop is bounded by the arguments.
 template <int SLOTS>
 __global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_compact_kernel(
     const uint16_t* __restrict__ rel, const double* __restrict__ part_vals,
@@ -645,18 +656,29 @@ __global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_compact_kernel(
     int64_t total_chunks, int64_t n_groups, double* __restrict__ out_sum,
     int64_t chunk) {
   __shared__ double lsum[SLOTS];
-  for (int64_t vc = blockIdx.x; vc < total_chunks; vc += gridDim.x) {
-    for (int i = threadIdx.x; i < SLOTS; i += blockDim.x) lsum[i] = 0.0;
+  const int tid = threadIdx.x;
+  const int64_t q = total_chunks / gridDim.x, rem = total_chunks % gridDim.x;
+  const int64_t bx = blockIdx.x;
+  int64_t vc = bx * q + (bx < rem ? bx : rem);
+  const int64_t vc1 = vc + q + (bx < rem ? 1 : 0);
+  if (vc >= vc1) return;
+  for (int i = tid; i < SLOTS; i += BLOCK) lsum[i] = 0.0;
+  __syncthreads();
+  while (vc < vc1) {
     const int b = bin_of(bin_chunk_base, nbins, vc);
-    int64_t start = bin_offsets[b] + (vc - bin_chunk_base[b]) * chunk;
-    int64_t end = start + chunk;
+    const int64_t cb = bin_chunk_base[b];
+    int64_t ve = bin_chunk_base[b + 1];
+    if (ve > vc1) ve = vc1;
+    if (ve <= vc) ve = vc + 1;  // progress whatever the bin arrays hold
+    const int64_t base = bin_group_base[b];
+    int64_t start = bin_offsets[b] + (vc - cb) * chunk;
+    int64_t end = bin_offsets[b] + (ve - cb) * chunk;
     const int64_t bin_end = bin_offsets[b + 1];
     if (end > bin_end) end = bin_end;
     // rows read stay inside [0, n) whatever the bin arrays hold
     if (start < 0) start = 0;
     if (end > n) end = n;
-    const int64_t base = bin_group_base[b];
-    __syncthreads();
+    if (start > end) start = end;
     auto add = [&](unsigned g, double v) {
       if (g < (unsigned)SLOTS) {
         atomicAdd(&lsum[g], v);
@@ -670,47 +692,54 @@ __global__ __launch_bounds__(BLOCK) void gb_dense_aggregate_compact_kernel(
     // of four and after the last go one per lane.
     int64_t a0 = (start + 3) & ~(int64_t)3;
     if (a0 > end) a0 = end;
-    const int64_t a1 = a0 + ((end - a0) & ~(int64_t)3);
-    {
-      int64_t h = start + threadIdx.x;
+    const int64_t ng = (end - a0) >> 2;  // four-row groups
+    const int64_t a1 = a0 + (ng << 2);
+    if (tid < 4) {
+      int64_t h = start + tid;
       if (h < a0) add(rel[h], part_vals[h]);
-      int64_t t = a1 + threadIdx.x;
+      int64_t t = a1 + tid;
       if (t < end) add(rel[t], part_vals[t]);
     }
-    const int64_t stride = (int64_t)blockDim.x * 4;
-    int64_t i = a0 + (int64_t)threadIdx.x * 4;
-    for (; i + stride < a1; i += 2 * stride) {
-      uint2 g0 = *(const uint2*)(rel + i);
-      uint2 g1 = *(const uint2*)(rel + i + stride);
-      double2 v0 = *(const double2*)(part_vals + i);
-      double2 v1 = *(const double2*)(part_vals + i + 2);
-      double2 v2 = *(const double2*)(part_vals + i + stride);
-      double2 v3 = *(const double2*)(part_vals + i + stride + 2);
-      add(g0.x & 0xffffu, v0.x);
-      add(g0.x >> 16, v0.y);
-      add(g0.y & 0xffffu, v1.x);
-      add(g0.y >> 16, v1.y);
-      add(g1.x & 0xffffu, v2.x);
-      add(g1.x >> 16, v2.y);
-      add(g1.y & 0xffffu, v3.x);
-      add(g1.y >> 16, v3.y);
+    if (ng > 0) {
+      const uint16_t* rp = rel + a0;
+      const double* vp = part_vals + a0;
+      uint2 ga, gb;
+      double2 va0, va1, vb0, vb1;
+      // group j of the interval, clamped to the last one
+      auto load = [&](uint2& g, double2& v0, double2& v1, int64_t j) {
+        if (j >= ng) j = ng - 1;
+        g = *(const uint2*)(rp + 4 * j);
+        v0 = *(const double2*)(vp + 4 * j);
+        v1 = *(const double2*)(vp + 4 * j + 2);
+      };
+      auto consume = [&](uint2 g, double2 v0, double2 v1, int64_t j) {
+        if (j < ng) {
+          add(g.x & 0xffffu, v0.x);
+          add(g.x >> 16, v0.y);
+          add(g.y & 0xffffu, v1.x);
+          add(g.y >> 16, v1.y);
+        }
+      };
+      load(ga, va0, va1, tid);
+      for (int64_t j = tid; j < ng; j += 2 * BLOCK) {
+        load(gb, vb0, vb1, j + BLOCK);  // in flight during the adds of j
+        consume(ga, va0, va1, j);
+        load(ga, va0, va1, j + 2 * BLOCK);
+        consume(gb, vb0, vb1, j + BLOCK);
+      }
     }
-    if (i < a1) {
-      uint2 g0 = *(const uint2*)(rel + i);
-      double2 v0 = *(const double2*)(part_vals + i);
-      double2 v1 = *(const double2*)(part_vals + i + 2);
-      add(g0.x & 0xffffu, v0.x);
-      add(g0.x >> 16, v0.y);
-      add(g0.y & 0xffffu, v1.x);
-      add(g0.y >> 16, v1.y);
-    }
+    vc = ve;
+    // flush and zero in one pass; the table is then ready for the next bin
     __syncthreads();
-    for (int s = threadIdx.x; s < SLOTS; s += blockDim.x) {
+    for (int s = tid; s < SLOTS; s += BLOCK) {
       double v = lsum[s];
-      if (v != 0.0 && (uint64_t)(base + s) < (uint64_t)n_groups)
-        atomicAdd(&out_sum[base + s], v);
+      if (v != 0.0) {
+        if ((uint64_t)(base + s) < (uint64_t)n_groups)
+          atomicAdd(&out_sum[base + s], v);
+        lsum[s] = 0.0;
+      }
     }
-    __syncthreads();
+    if (vc < vc1) __syncthreads();
   }
 }
 
@@ -878,6 +907,44 @@ hipError_t scatter_tile_compact_launch(
                      rank, tile_start, tile_delta, nbins, n, tile, out);
   return hipGetLastError();
 }
+
+// The grid is the blocks the device holds at once (CUs x blocks per CU at
+// this instantiation's LDS, asked once per device), each with one
+// contiguous range of the virtual chunks.
+template <int SLOTS>
+void dense_aggregate_compact_launch(
+    const uint16_t* rel, const double* part_vals, int64_t n,
+    const int64_t* bin_offsets, const int64_t* bin_group_base,
+    const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
+    int64_t n_groups, double* out_sum, int64_t chunk, hipStream_t stream) {
+  static int resident[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+  int grid = dev >= 0 && dev < 64 ? resident[dev] : 0;
+  if (grid == 0) {
+    int cus = 0, per_cu = 0;
+    if (dev < 0 ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess ||
+        cus < 1)
+      cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu,
+            reinterpret_cast<const void*>(
+                &gb_dense_aggregate_compact_kernel<SLOTS>),
+            BLOCK, 0) != hipSuccess ||
+        per_cu < 1)
+      per_cu = 1;
+    grid = cus * per_cu;
+    if (grid > MAX_GRID) grid = MAX_GRID;
+    if (dev >= 0 && dev < 64) resident[dev] = grid;
+  }
+  if (total_chunks < grid) grid = (int)total_chunks;
+  hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<SLOTS>), dim3(grid),
+                     dim3(BLOCK), 0, stream, rel, part_vals, n, bin_offsets,
+                     bin_group_base, bin_chunk_base, nbins, total_chunks,
+                     n_groups, out_sum, chunk);
+}
 }  // namespace
 
 extern "C" {
@@ -905,25 +972,21 @@ void launch_gb_dense_aggregate_compact(
     const int64_t* bin_chunk_base, int nbins, int64_t total_chunks,
     int64_t n_groups, double* out_sum, int64_t chunk, int slots,
     hipStream_t stream) {
-  dim3 g(chunk_grid(total_chunks, 1)), b(BLOCK);
   switch (slots) {
     case 2048:
-      hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<2048>), g, b, 0,
-                         stream, rel, part_vals, n, bin_offsets,
-                         bin_group_base, bin_chunk_base, nbins, total_chunks,
-                         n_groups, out_sum, chunk);
+      dense_aggregate_compact_launch<2048>(
+          rel, part_vals, n, bin_offsets, bin_group_base, bin_chunk_base,
+          nbins, total_chunks, n_groups, out_sum, chunk, stream);
       break;
     case 4096:
-      hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<4096>), g, b, 0,
-                         stream, rel, part_vals, n, bin_offsets,
-                         bin_group_base, bin_chunk_base, nbins, total_chunks,
-                         n_groups, out_sum, chunk);
+      dense_aggregate_compact_launch<4096>(
+          rel, part_vals, n, bin_offsets, bin_group_base, bin_chunk_base,
+          nbins, total_chunks, n_groups, out_sum, chunk, stream);
       break;
     default:
-      hipLaunchKernelGGL((gb_dense_aggregate_compact_kernel<8192>), g, b, 0,
-                         stream, rel, part_vals, n, bin_offsets,
-                         bin_group_base, bin_chunk_base, nbins, total_chunks,
-                         n_groups, out_sum, chunk);
+      dense_aggregate_compact_launch<8192>(
+          rel, part_vals, n, bin_offsets, bin_group_base, bin_chunk_base,
+          nbins, total_chunks, n_groups, out_sum, chunk, stream);
   }
 }
 

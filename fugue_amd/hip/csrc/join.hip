@@ -364,7 +364,8 @@ __global__ __launch_bounds__(BLOCK) void join_mark_build_kernel(
 // ------------------------------------------------------------------ //
 // fused unique inner join + residual comparison + projection          //
 //                                                                     //
-// One block per COMPACT_CHUNK probe rows, grid-stride.  Phase A is the //
+// One block per ROWS probe rows (COMPACT_CHUNK, or fewer for a small   //
+// probe side: launch_join_unique_select), grid-stride.  Phase A is the //
 // ILP-4 chain walk of join_left_unique_kernel over the block's chunk   //
 // (the dependent random loads heads -> bkeys/next bound the kernel);   //
 // the comparison runs on the matched rows and the surviving match      //
@@ -395,23 +396,27 @@ __device__ __forceinline__ bool jsel_pred(const JoinSelPred& p, int64_t i,
   return cmp_apply<double>(x, y, p.op);
 }
 
+// ROWS probe rows per block (a multiple of 4 * BLOCK): COMPACT_CHUNK for
+// large probes, fewer for small ones so that the grid fills the device
+template <int ROWS>
 __global__ __launch_bounds__(BLOCK) void join_unique_select_kernel(
     const int64_t* __restrict__ pkeys, int64_t np,
     const int64_t* __restrict__ bkeys, const int32_t* __restrict__ heads,
     const int32_t* __restrict__ next, int64_t tsize, JoinSelPred pred,
     JoinSelCols cols, int64_t* __restrict__ cursor) {
-  __shared__ int32_t smatch[COMPACT_CHUNK];  // surviving match or -1
+  static_assert(ROWS % (4 * BLOCK) == 0, "whole rounds of four rows");
+  __shared__ int32_t smatch[ROWS];  // surviving match or -1
   __shared__ int lcount;
   __shared__ long long lbase;
   uint64_t tmask = (uint64_t)(tsize - 1);
-  for (int64_t start = (int64_t)blockIdx.x * COMPACT_CHUNK; start < np;
-       start += (int64_t)gridDim.x * COMPACT_CHUNK) {
-    int64_t end = start + COMPACT_CHUNK;
+  for (int64_t start = (int64_t)blockIdx.x * ROWS; start < np;
+       start += (int64_t)gridDim.x * ROWS) {
+    int64_t end = start + ROWS;
     if (end > np) end = np;
     if (threadIdx.x == 0) lcount = 0;
     __syncthreads();
     int local = 0;
-    for (int g = 0; g < COMPACT_CHUNK / BLOCK; g += 4) {
+    for (int g = 0; g < ROWS / BLOCK; g += 4) {
       int64_t idx[4], key[4];
       int32_t cur[4], match[4];
 #pragma unroll
@@ -460,7 +465,7 @@ __global__ __launch_bounds__(BLOCK) void join_unique_select_kernel(
     }
     __syncthreads();
     // a thread reads back only the slots it wrote
-    for (int r = 0; r < COMPACT_CHUNK / BLOCK; ++r) {
+    for (int r = 0; r < ROWS / BLOCK; ++r) {
       int32_t m = smatch[r * BLOCK + threadIdx.x];
       if (m < 0) continue;
       int64_t i = start + (int64_t)r * BLOCK + threadIdx.x;
@@ -478,18 +483,53 @@ __global__ __launch_bounds__(BLOCK) void join_unique_select_kernel(
   }
 }
 
+namespace {
+// CUs of the current device, asked once per device
+int device_cus() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int c = 0;
+    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess ||
+        c < 1)
+      c = 256;
+    cus[dev] = c;
+  }
+  return cus[dev];
+}
+}  // namespace
+
 extern "C" {
 
+// block_rows: probe rows per block, 1024, 2048 or COMPACT_CHUNK; 0 picks
+// the largest that still gives every CU four blocks (a block is one wave
+// per SIMD, and the chain walk is bound by latency), else the smallest
 void launch_join_unique_select(const int64_t* pkeys, int64_t np,
                                const int64_t* bkeys, const int32_t* heads,
                                const int32_t* next, int64_t tsize,
                                const JoinSelPred* pred,
                                const JoinSelCols* cols, int64_t* cursor,
-                               hipStream_t stream) {
-  hipLaunchKernelGGL(join_unique_select_kernel,
-                     dim3(chunk_grid(np, COMPACT_CHUNK)), dim3(BLOCK), 0,
-                     stream, pkeys, np, bkeys, heads, next, tsize, *pred,
-                     *cols, cursor);
+                               int block_rows, hipStream_t stream) {
+  if (block_rows <= 0) {
+    const int64_t want = (int64_t)4 * device_cus();
+    block_rows = COMPACT_CHUNK;
+    while (block_rows > 1024 && np / block_rows < want) block_rows /= 2;
+  }
+#define JSEL_RUN(ROWS)                                                     \
+  hipLaunchKernelGGL(join_unique_select_kernel<ROWS>,                      \
+                     dim3(chunk_grid(np, ROWS)), dim3(BLOCK), 0, stream,   \
+                     pkeys, np, bkeys, heads, next, tsize, *pred, *cols,   \
+                     cursor)
+  if (block_rows >= COMPACT_CHUNK) {
+    JSEL_RUN(COMPACT_CHUNK);
+  } else if (block_rows >= 2048) {
+    JSEL_RUN(2048);
+  } else {
+    JSEL_RUN(1024);
+  }
+#undef JSEL_RUN
 }
 
 void launch_join_build(const int64_t* keys, int64_t n, int32_t* heads,

@@ -271,13 +271,14 @@ void launch_join_mark_build(const int64_t* pkeys, int64_t np,
 // the number of rows written on exit; rows land in no defined order.  Any
 // int64 key value is admitted.  A build key that occurs twice makes the
 // walk stop at the first match in chain order: the caller must not use
-// the result then.
+// the result then.  block_rows: probe rows per block, 1024, 2048 or
+// COMPACT_CHUNK; 0 lets the launcher pick by np and the device's CUs.
 void launch_join_unique_select(const int64_t* pkeys, int64_t np,
                                const int64_t* bkeys, const int32_t* heads,
                                const int32_t* next, int64_t tsize,
                                const JoinSelPred* pred,
                                const JoinSelCols* cols, int64_t* cursor,
-                               hipStream_t stream);
+                               int block_rows, hipStream_t stream);
 void launch_joinoa_build(const int64_t* bkeys, int64_t nb, int64_t* table,
                          int64_t tsize, int64_t* flags, hipStream_t stream);
 void launch_joinoa_probe(const int64_t* pkeys, int64_t np,
