@@ -663,9 +663,16 @@ class HipExecutionEngine(ExecutionEngine):
         local = 1 if c.valid is not None else 0
         return self._comm.allreduce_sum(local) > 0
 
-    def _shuffle_by_columns(self, df: HipDataFrame, keys: List[str]) -> HipDataFrame:
+    def _shuffle_by_columns(
+        self, df: HipDataFrame, keys: List[str], by_value: bool = False
+    ) -> HipDataFrame:
+        """``by_value``: equal values share a rank even where their bits
+        differ (the two float zeros, NaN and null) — set operations."""
         with op_range("fugue.shuffle.hash"):
-            hashes = dops.hash_rows([df.col(k) for k in keys])
+            cols = [df.col(k) for k in keys]
+            if by_value:
+                cols = self._canonical_key_cols(cols)
+            hashes = dops.hash_rows(cols)
             part, counts = dops.partition_by_hash(df, hashes, self.world_size)
             return self._exchange(part, counts)
 
@@ -876,19 +883,61 @@ class HipExecutionEngine(ExecutionEngine):
             return self._gather_all(df)
         return df.as_local()
 
+    @staticmethod
+    def _check_join_key_types(
+        d1: HipDataFrame, d2: HipDataFrame, keys: List[str]
+    ) -> None:
+        """Device joins compare keys of one type, or of two integer
+        widths.  Every other pairing (int against float, float32 against
+        float64, temporal or string against anything else) has no exact
+        common device key and takes the host join.  Decided from the two
+        schemas alone, so every rank decides alike."""
+        for k in keys:
+            t1, t2 = d1.schema[k].type, d2.schema[k].type
+            if t1 == t2 or (pa.types.is_integer(t1) and pa.types.is_integer(t2)):
+                continue
+            raise NotImplementedError(f"join key {k}: {t1} against {t2}")
+
+    @staticmethod
+    def _canonical_key_cols(cols: List[DeviceColumn]) -> List[DeviceColumn]:
+        """Columns whose raw bits are equal exactly where their values are:
+        float columns get one zero (``-0.0 + 0.0`` is ``0.0``) and NaN
+        joins the null class (a host frame cannot tell the two apart).
+        The hash kernels compare bits and stay that way."""
+        out: List[DeviceColumn] = []
+        for c in cols:
+            if not isinstance(c, StringDeviceColumn) and c.data.is_floating_point():
+                ok = ~torch.isnan(c.data)
+                if c.valid is not None:
+                    ok = ok & c.valid
+                c = DeviceColumn(c.data + 0.0, ok, c.pa_type)
+            out.append(c)
+        return out
+
     def _join_keys(
         self, d1: HipDataFrame, d2: HipDataFrame, keys: List[str]
     ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
-        """Comparable join keys for both sides: exact packed int64 when
-        the key tuple fits 63 bits; otherwise 128-bit hashed keys
-        (h1 compared in the table, h2 verified — string keys)."""
+        """Comparable join keys for both sides: exact int64 when the key
+        is one float column (its canonical bit pattern) or an integer
+        tuple that fits 63 bits; otherwise 128-bit hashed keys (h1
+        compared in the table, h2 verified — string keys, float columns
+        in a wider key, wide integer tuples)."""
         try:
             k1, k2 = self._shared_key_pack(d1, d2, keys)
             return k1, k2, None, None
         except NotImplementedError:
             pass
-        c1 = [d1.col(k) for k in keys]
-        c2 = [d2.col(k) for k in keys]
+        c1 = self._canonical_key_cols([d1.col(k) for k in keys])
+        c2 = self._canonical_key_cols([d2.col(k) for k in keys])
+        for i, (a, b) in enumerate(zip(c1, c2)):
+            # two integer widths hash alike only once they are one width
+            if (
+                not isinstance(a, StringDeviceColumn)
+                and not isinstance(b, StringDeviceColumn)
+                and a.data.dtype != b.data.dtype
+            ):
+                c1[i] = DeviceColumn(a.data.to(torch.int64), a.valid, pa.int64())
+                c2[i] = DeviceColumn(b.data.to(torch.int64), b.valid, pa.int64())
         k1 = dops.hash_rows(c1)
         k2 = dops.hash_rows(c2)
         h21 = dops.hash_rows(c1, seed=dops._H2_SEED)
@@ -899,7 +948,8 @@ class HipExecutionEngine(ExecutionEngine):
         self, d1: HipDataFrame, d2: HipDataFrame, keys: List[str]
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Pack join keys of both sides into comparable int64 keys (shared
-        offsets, allreduced across ranks)."""
+        offsets, allreduced across ranks).  The route depends on the key
+        columns' types only, never on their values."""
         cols1 = [d1.col(k) for k in keys]
         cols2 = [d2.col(k) for k in keys]
         if (
@@ -912,13 +962,20 @@ class HipExecutionEngine(ExecutionEngine):
             and cols2[0].valid is None
         ):
             return cols1[0].data, cols2[0].data
-        mins: List[int] = []
-        widths: List[int] = []
         for c1, c2 in zip(cols1, cols2):
             if isinstance(c1, StringDeviceColumn) or isinstance(
                 c2, StringDeviceColumn
             ):
                 raise NotImplementedError("string join keys")
+        if any(
+            c.data.is_floating_point() for c in list(cols1) + list(cols2)
+        ):
+            if len(keys) > 1:
+                raise NotImplementedError("float column in a multi-column key")
+            return self._float_bits_key(cols1[0]), self._float_bits_key(cols2[0])
+        mins: List[int] = []
+        widths: List[int] = []
+        for c1, c2 in zip(cols1, cols2):
             lo = min(self._global_min(c1), self._global_min(c2))
             hi = max(self._global_max(c1), self._global_max(c2))
             mins.append(lo)
@@ -929,7 +986,22 @@ class HipExecutionEngine(ExecutionEngine):
         k2, _ = dops.pack_keys(cols2, mins=mins, widths=widths)
         return k1, k2
 
+    @staticmethod
+    def _float_bits_key(c: DeviceColumn) -> torch.Tensor:
+        """The exact int64 key of one float column: the bit pattern of the
+        value with ``-0.0`` folded into ``0.0``.  Two floats of one type
+        are equal exactly when these are (null and NaN rows were split
+        off before, ``_split_null_keys``)."""
+        data = (c.data + 0.0).contiguous()
+        if data.dtype == torch.float64:
+            return data.view(torch.int64)
+        if data.dtype == torch.float32:
+            return data.view(torch.int32).to(torch.int64)
+        raise NotImplementedError(f"float join key of {data.dtype}")
+
     def _global_min(self, c: DeviceColumn) -> int:
+        if c.data.is_floating_point():
+            raise NotImplementedError("float key column has no integer range")
         v = int(c.data.min().item()) if len(c) > 0 else 0
         if self.is_distributed:
             v = self._allreduce_min(v)
@@ -944,6 +1016,8 @@ class HipExecutionEngine(ExecutionEngine):
         return int(t.cpu().item())
 
     def _global_max(self, c: DeviceColumn) -> int:
+        if c.data.is_floating_point():
+            raise NotImplementedError("float key column has no integer range")
         v = int(c.data.max().item()) if len(c) > 0 else 0
         if self.is_distributed:
             import torch.distributed as dist
@@ -966,6 +1040,7 @@ class HipExecutionEngine(ExecutionEngine):
         """``post``: the join's consumer (``join_select``).  Answered here,
         with ``post.done`` set, only by the fused local join; the
         broadcast and co-shuffle steps before it are the same either way."""
+        self._check_join_key_types(d1, d2, keys)
         # null keys never match: split them out first
         d1v, d1n = self._split_null_keys(d1, keys)
         d2v, _d2n = self._split_null_keys(d2, keys)
@@ -982,10 +1057,11 @@ class HipExecutionEngine(ExecutionEngine):
                 # with d1 replicated and d2 sharded, the local joins union
                 # to the right answer for inner joins
             else:
-                k1t, _, _, _ = self._join_keys(d1v, d1v, keys)
+                # one key space for both sides: keys packed per side
+                # (own offsets) would send equal values to different ranks
+                k1t, k2t, _, _ = self._join_keys(d1v, d2v, keys)
                 d1v = self._shuffle_by_tensor_key(d1v, k1t)
-                k2t2, _, _, _ = self._join_keys(d2v, d2v, keys)
-                d2v = self._shuffle_by_tensor_key(d2v, k2t2)
+                d2v = self._shuffle_by_tensor_key(d2v, k2t)
         k1, k2, h21, h22 = self._join_keys(d1v, d2v, keys)
         if how in ("inner", "left_outer", "semi", "anti"):
             mode = {
@@ -1192,12 +1268,26 @@ class HipExecutionEngine(ExecutionEngine):
     def _split_null_keys(
         self, df: HipDataFrame, keys: List[str]
     ) -> Tuple[HipDataFrame, HipDataFrame]:
+        """(rows whose key can match, rows whose key is null).  A NaN
+        in a float key counts as null, as it does in every host frame."""
         mask: Optional[torch.Tensor] = None
         for k in keys:
             c = df.col(k)
             if c.valid is not None:
                 m = c.valid
                 mask = m if mask is None else (mask & m)
+            if (
+                not isinstance(c, StringDeviceColumn)
+                and c.data.is_floating_point()
+            ):
+                nan = torch.isnan(c.data)
+                # on one rank the frame keeps its mask-free columns (and
+                # the fused join its input) unless a NaN is really there.
+                # Ranks must not part ways on their own data: a frame
+                # that is split is a new object, and the per-frame memos
+                # of _global_bytes / _replicate hold collectives
+                if self.is_distributed or bool(nan.any().item()):
+                    mask = ~nan if mask is None else (mask & ~nan)
         if mask is None:
             return df, df.slice_rows(0, 0)
         valid_idx = mask.nonzero(as_tuple=True)[0]
@@ -1241,7 +1331,30 @@ class HipExecutionEngine(ExecutionEngine):
             name = f.name
             if name in probe.schema._index:
                 src = probe_gather.col(name)
-                # keys come from the left frame per fugue semantics
+                # keys come from the left frame per fugue semantics.  With
+                # the right frame as probe (right outer) an equal key may
+                # still differ from the left's: in width (two integer
+                # types) and, for floats, in the sign of a zero
+                if not probe_is_left and name in keys:
+                    src = self._as_type(src, f.type)
+                    if (
+                        build.count() > 0
+                        and not isinstance(src, StringDeviceColumn)
+                        and src.data.is_floating_point()
+                    ):
+                        # a left frame of key columns alone is not
+                        # gathered as a whole: fetch this column then
+                        left_key = (
+                            build_gather.col(name)
+                            if build_gather is not None
+                            else build.col(name).gather(bi_safe)
+                        ).data
+                        data = (
+                            left_key
+                            if build_invalid is None
+                            else torch.where(build_invalid, src.data, left_key)
+                        )
+                        src = DeviceColumn(data, src.valid, src.pa_type)
                 cols[name] = src
             elif build_gather is None:
                 cols[name] = self._null_column(f.type, int(pi.numel()))
@@ -1280,10 +1393,21 @@ class HipExecutionEngine(ExecutionEngine):
         cols: Dict[str, DeviceColumn] = {}
         for f in output_schema.fields:
             if f.name in right.schema._index:
-                cols[f.name] = right.col(f.name)
+                # a key column takes the left frame's type
+                cols[f.name] = self._as_type(right.col(f.name), f.type)
             else:
                 cols[f.name] = self._null_column(f.type, n)
         return HipDataFrame.from_columns(cols, output_schema, self._device)
+
+    @staticmethod
+    def _as_type(c: DeviceColumn, tp: pa.DataType) -> DeviceColumn:
+        """``c`` as a column of type ``tp`` (two integer widths of a join
+        key; the device join admits no other difference)."""
+        if isinstance(c, StringDeviceColumn) or c.pa_type == tp:
+            return c
+        from fugue_amd.hip.frame import _torch_dtype_for
+
+        return DeviceColumn(c.data.to(_torch_dtype_for(tp)), c.valid, tp)
 
     def _null_column(self, tp: pa.DataType, n: int) -> DeviceColumn:
         device = torch.device(self._device)
@@ -1340,8 +1464,9 @@ class HipExecutionEngine(ExecutionEngine):
     def _row_keys(
         self, d: HipDataFrame
     ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """128-bit row-content keys (nulls form their own value class)."""
-        cols = [d.col(n) for n in d.schema.names]
+        """128-bit row-content keys by value: nulls (and NaN with them)
+        form one class of their own, and both zeros are one value."""
+        cols = self._canonical_key_cols([d.col(n) for n in d.schema.names])
         return (
             dops.hash_rows(cols),
             dops.hash_rows(cols, seed=dops._H2_SEED),
@@ -1362,8 +1487,8 @@ class HipExecutionEngine(ExecutionEngine):
             return None  # INTERSECT ALL: rare, host path
         try:
             if self.is_distributed:
-                d1 = self._shuffle_by_columns(d1, d1.schema.names)
-                d2 = self._shuffle_by_columns(d2, d2.schema.names)
+                d1 = self._shuffle_by_columns(d1, d1.schema.names, True)
+                d2 = self._shuffle_by_columns(d2, d2.schema.names, True)
             h11, h12 = self._row_keys(d1)
             h21, h22 = self._row_keys(d2)
             pi, _bi = dops.hash_join_indices(h11, h21, how, h12, h22)
@@ -1389,8 +1514,8 @@ class HipExecutionEngine(ExecutionEngine):
             # co-shuffle both by full-row hash, then local set op
             cols = d1.schema.names
             try:
-                d1 = self._shuffle_by_columns(d1, cols)
-                d2 = self._shuffle_by_columns(d2, cols)
+                d1 = self._shuffle_by_columns(d1, cols, True)
+                d2 = self._shuffle_by_columns(d2, cols, True)
             except NotImplementedError:
                 d1l, d2l = self._gather_all(d1), self._gather_all(d2)
                 return self._local_setop(d1l, d2l, distinct, op, shard=True)
@@ -1416,7 +1541,7 @@ class HipExecutionEngine(ExecutionEngine):
         if isinstance(d, HipDataFrame):
             try:
                 if self.is_distributed:
-                    d = self._shuffle_by_columns(d, d.schema.names)
+                    d = self._shuffle_by_columns(d, d.schema.names, True)
                 h1, h2 = self._row_keys(d)
                 reps = dops.distinct_reps(h1, h2)
                 return d.gather_rows(reps.to(h1.device))

@@ -126,7 +126,11 @@ class DeviceColumn:
             valid_np = ~np.asarray(arr.is_null())
             valid_t = torch.from_numpy(valid_np).to(device)
             if pa.types.is_floating(tp):
-                np_arr = np.nan_to_num(np_arr, nan=0.0)
+                # the null slots only: nan_to_num's defaults would also
+                # turn +-inf into the largest finite values
+                np_arr = np.nan_to_num(
+                    np_arr, nan=0.0, posinf=np.inf, neginf=-np.inf
+                )
             elif np_arr.dtype == np.dtype("object") or np_arr.dtype.kind == "f":
                 # ints with nulls come back as float; fill and cast
                 np_arr = np.nan_to_num(np_arr.astype("float64"), nan=0.0)

@@ -195,3 +195,61 @@ def test_string_key_shuffle():
         assert got["k"].tolist() == exp["k"].tolist()
         np.testing.assert_allclose(got["s"], exp["s"], rtol=1e-9)
         np.testing.assert_allclose(got["w"], exp["w"], rtol=1e-12)
+
+
+def _float_key_job(rank: int):
+    """Inner and left joins on a fractional double key (quarters share
+    their integer parts; both zeros, +-inf and a NaN are among them), the
+    right side broadcast and — with a zero broadcast threshold — both
+    sides co-shuffled by key."""
+    from fugue_amd.hip.execution_engine import HipExecutionEngine
+
+    from fugue_amd import PandasDataFrame
+    from fugue_amd.hip.frame import HipDataFrame
+
+    rng = np.random.default_rng(40 + rank)
+    special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 2.0 ** 53])
+    n = 300 + 50 * rank
+    lk = np.concatenate([special, rng.integers(-40, 40, n) / 4.0])
+    left = pd.DataFrame(dict(k=lk, lv=np.arange(len(lk)) + 1000 * rank))
+    rk = np.concatenate([special[rank::4], np.arange(-30 + rank, 30, 4) / 4.0])
+    right = pd.DataFrame(dict(k=rk, rv=np.arange(len(rk)) * 0.5 + rank))
+    out = dict(left=left.to_dict("list"), right=right.to_dict("list"))
+    for tag, conf in (("bcast", None), ("shuffle", {"fugue.hip.broadcast_threshold_bytes": 0})):
+        e = HipExecutionEngine(conf)
+        # from_pandas would turn the NaN into a null: same class, fine here
+        l = HipDataFrame(
+            PandasDataFrame(left, "k:double,lv:long").as_arrow(),
+            "k:double,lv:long", device=e.device,
+        )
+        r = HipDataFrame(
+            PandasDataFrame(right, "k:double,rv:double").as_arrow(),
+            "k:double,rv:double", device=e.device,
+        )
+        for how in ("inner", "left_outer"):
+            res = e._gather_all(e.join(l, r, how=how, on=["k"]))
+            out[f"{tag}-{how}"] = [tuple(x) for x in res.as_array()]
+    return out
+
+
+def test_float_key_joins():
+    from collections import Counter
+
+    import join_setop_refs as R
+
+    results = run_world4(_float_key_job, 29623)
+    left = pd.concat(
+        [pd.DataFrame(results[r]["left"]) for r in range(WORLD)], ignore_index=True
+    )
+    right = pd.concat(
+        [pd.DataFrame(results[r]["right"]) for r in range(WORLD)], ignore_index=True
+    )
+    lrows = [(float(k), int(v)) for k, v in zip(left["k"], left["lv"])]
+    rrows = [(float(k), float(v)) for k, v in zip(right["k"], right["rv"])]
+    for how in ("inner", "left_outer"):
+        want = R.join_ref(lrows, rrows, [(0, 0)], how)
+        assert sum(want.values()) > len(lrows) // 2
+        for tag in ("bcast", "shuffle"):
+            for r in range(WORLD):
+                got = Counter(R.cells(x) for x in results[r][f"{tag}-{how}"])
+                assert got == want, (tag, how, r)
